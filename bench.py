@@ -11,7 +11,9 @@ all-gather of the finished waveforms (audiodiffuser_amd/distributed.py).
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
 (torch.distributed.run, one process per GPU, before this process touches a GPU); under torchrun it is one rank.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement); extra objects:
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run sets up, warms up, times the
+--steps sampler runs, writes the last one's waveforms if --dump-outputs DIR is given, and prints the line.  `--full` adds
+the measurements below, each of which takes runs of its own (the --no-* options drop single ones of them):
   roofline     -- the dominant kernel (fused resblock implicit GEMM): algorithmic bytes / flops per launch
                   over its HIP-event-timed launch duration, replayed exactly as the network pass issues it on rotating
                   operand copies (adf_bench_resblock); `traffic` = HBM bytes per launch from two rocprofv3 --pmc passes
@@ -19,6 +21,7 @@ Prints ONE JSON line on rank 0 (see the driver contract in the task statement); 
   cpu_baseline -- the CPU oracle (a port of the reference PyTorch path) timed on the host cores: the same workload on a
                   bounded sample (`value`), and SURVEY.md 8(d)'s protocol on BASELINE configs[0] (`config1`)
   bf16_vs_fp32 -- deviation of the timed (bf16) run's first waveforms from the fp32 (parity-grade) mode on the same noise
+  other_workloads -- the configs[2] / [3] / [4] lines as child runs (default workload only)
 """
 from __future__ import annotations
 
@@ -62,6 +65,10 @@ def parse(argv=None):
     ap.add_argument("--num-steps", type=int, default=None, help="sigma schedule length N (Heun => 2N-1 NFE; default 50; c5: 6)")
     ap.add_argument("--sampler", default=None, choices=["heun", "dpm", "churn"], help="default: heun; dpm for --config c3; churn (the stochastic EDM sampler of configs[3]) for c4")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the line's own steps, also measure the roofline, PMC traffic, other precisions and workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's waveforms as DIR/samples.npy (float32; a seeded sample of rows beyond 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline.traffic = null)")
     ap.add_argument("--no-precision-check", action="store_true", help="skip the fp32 run behind bf16_vs_fp32")
@@ -551,7 +558,7 @@ def other_workloads(a):
     out = {}
     for name, argv in (("c3", ["--config", "c3", "--sampler", "dpm"]), ("c4", ["--config", "c4"]), ("c5", ["--config", "c5"])):
         # (configs[3] / [4] also collect their PMC traffic -- two rocprofv3 passes each, ~30 s -- so that the figure rides in the driver's line)
-        cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + (["--no-pmc"] if name == "c3" else []) + [
+        cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"] + (["--no-pmc"] if name == "c3" else []) + [
                "--no-precision-check", "--no-other-workloads", "--roofline-iters", "10"]
         t0 = time.perf_counter()
         try:
@@ -605,6 +612,22 @@ def timed_steps(a, step, fence, world, device, dist):
     return out, dt
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out):
+    """`--dump-outputs DIR`: the waveforms (mel blocks for c4) the last timed step returned, as DIR/samples.npy in float32,
+    so that two builds can be compared output for output on the same seeded inputs.  Beyond DUMP_LIMIT_BYTES only a fixed,
+    seeded sample of rows (whole waveforms, ascending order) is written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    x = out.detach().float().cpu().numpy()
+    if x.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, DUMP_LIMIT_BYTES // x[0].nbytes)
+        x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], keep, replace=False))]
+    np.save(os.path.join(path, "samples.npy"), x)
+
+
 def base_line(a, world, dist, dt, value, metric, unit, workload, nfe, finite, clamped):
     """The fields of the one JSON line that do not depend on the device layer."""
     global_batch = a.batch * world
@@ -647,6 +670,8 @@ def mock_ranks(a, world, rank, dist):
     res["gathered_shape"] = list(out.shape)
     res["gathered_checksum"] = float(out.double().sum())
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, out)
         print(json.dumps(res))
     if world > 1:
         dist.barrier()
@@ -757,80 +782,83 @@ def main():
                     f"{a.sampler}, batch {a.batch}/GPU, random-init weights", nfe, finite, clamped)
     res["device_loop"] = hd.counters()            # adf_get_counters: the timed steps were hipGraph replays of adf_sampler_run
     if rank == 0:
-        net(noise[:a.batch], torch.zeros(a.batch, device=device))       # one eager pass: the replay reads its operands
-        torch.cuda.synchronize()
-        if adm:
-            rf = adm_roofline(net, cfg, noise[:a.batch], device, a.dtype)
-        elif wavenet:
-            rf = wavenet_roofline(hd, cfg, a.batch, a.length, a.dtype, min(a.roofline_iters, 10), device)
-        else:
-            rf = roofline(hd, a.batch, a.length, a.dtype, a.roofline_iters, device)
-        res["roofline"] = rf
-        if rf and world == 1 and not a.no_pmc:
-            traffic, detail = pmc_traffic(a, rf["level"], rf["conv"])
-            rf["traffic"] = traffic
-            rf["traffic_source"] = detail
-        if a.dtype == "bf16" and not a.no_precision_check:
-            # the parity-grade (fp32) mode on the same noise: what the storage precision costs the audio.  On the headline
-            # workload the fp32 mode runs the WHOLE batch and its second (graph-replayed) run is timed: the throughput of the
-            # mode that meets the north star's <= 1e-3 bar (`fp32_mode_ms_per_step`)
-            full = a.config == "c2" and world == 1
-            nb = a.batch if full else min(2, a.batch)
-            net32 = make_net("fp32")
-            net32.load_state_dict(make_weights())
-            net32 = net32.to(device)
-            t1 = time.perf_counter()
-            extra32 = {k: v[:, :nb].contiguous() for k, v in extra.items()}       # the same per-step draws as the timed run
-            n32 = noise[:nb].contiguous()
-            y32 = sampler(n32, fn=diff.denoise_fn, net=net32, sigmas=sigmas, **extra32)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, out)
+        if a.full:
+            net(noise[:a.batch], torch.zeros(a.batch, device=device))       # one eager pass: the replay reads its operands
             torch.cuda.synchronize()
-            t32 = time.perf_counter() - t1
-            if full:
+            if adm:
+                rf = adm_roofline(net, cfg, noise[:a.batch], device, a.dtype)
+            elif wavenet:
+                rf = wavenet_roofline(hd, cfg, a.batch, a.length, a.dtype, min(a.roofline_iters, 10), device)
+            else:
+                rf = roofline(hd, a.batch, a.length, a.dtype, a.roofline_iters, device)
+            res["roofline"] = rf
+            if rf and world == 1 and not a.no_pmc:
+                traffic, detail = pmc_traffic(a, rf["level"], rf["conv"])
+                rf["traffic"] = traffic
+                rf["traffic_source"] = detail
+            if a.dtype == "bf16" and not a.no_precision_check:
+                # the parity-grade (fp32) mode on the same noise: what the storage precision costs the audio.  On the headline
+                # workload the fp32 mode runs the WHOLE batch and its second (graph-replayed) run is timed: the throughput of the
+                # mode that meets the north star's <= 1e-3 bar (`fp32_mode_ms_per_step`)
+                full = a.config == "c2" and world == 1
+                nb = a.batch if full else min(2, a.batch)
+                net32 = make_net("fp32")
+                net32.load_state_dict(make_weights())
+                net32 = net32.to(device)
                 t1 = time.perf_counter()
+                extra32 = {k: v[:, :nb].contiguous() for k, v in extra.items()}       # the same per-step draws as the timed run
+                n32 = noise[:nb].contiguous()
                 y32 = sampler(n32, fn=diff.denoise_fn, net=net32, sigmas=sigmas, **extra32)
                 torch.cuda.synchronize()
-                t32b = time.perf_counter() - t1
-                res["fp32_mode_ms_per_step"] = t32b * 1e3
-                res["fp32_mode"] = {"ms_per_step": t32b * 1e3, "value": nb * a.length / t32b, "unit": res["unit"], "waveforms_per_s": nb / t32b, "batch": nb,
-                                    "note": "same workload in the fp32 (parity-grade, exact-fp32 MFMA) mode: one graph-replayed sampler run after the capturing one"}
-                # the split-bf16 mode (ADF_DTYPE_F32X3: fp32 storage, bf16 hi + lo operands, three bf16 MFMAs per product) on the same workload: the
-                # in-tolerance mode meant to be USED (tests/test_gpu_parity.py::test_config2_full_sampler_fp32_vs_oracle holds it to the oracle at 1e-3)
-                netx = make_net("f32x3")
-                netx.load_state_dict(make_weights())
-                netx = netx.to(device)
-                yx = sampler(n32, fn=diff.denoise_fn, net=netx, sigmas=sigmas, **extra32)
-                torch.cuda.synchronize()
-                t1 = time.perf_counter()
-                yx = sampler(n32, fn=diff.denoise_fn, net=netx, sigmas=sigmas, **extra32)
-                torch.cuda.synchronize()
-                tx = time.perf_counter() - t1
-                dx = yx.to(torch.float64) - y32.to(torch.float64)
-                res["f32x3_mode_ms_per_step"] = tx * 1e3
-                res["f32x3_mode"] = {"ms_per_step": tx * 1e3, "value": nb * a.length / tx, "unit": res["unit"], "waveforms_per_s": nb / tx, "batch": nb,
-                                     "vs_fp32_rel_l2": float(dx.norm() / y32.to(torch.float64).norm()),
-                                     "vs_fp32_max_abs_over_max": float(dx.abs().max() / y32.abs().max()),
-                                     "note": "same workload in the split-bf16 mode (fp32 storage; every GEMM operand as bf16 hi + lo, 3 bf16 MFMAs per product, fp32 "
-                                             "accumulation); deviation from the exact-fp32 mode over the whole 99-evaluation sampler on all waveforms"}
-                del netx, yx
-            y16 = out[:nb].to(torch.float64)
-            d = y16 - y32.to(torch.float64)
-            res["bf16_vs_fp32"] = {"waveforms": nb, "rel_l2": float(d.norm() / y32.to(torch.float64).norm()),
-                                   "max_abs_over_max": float(d.abs().max() / y32.abs().max()),
-                                   "note": "bf16 run (the timed one) against the fp32 mode (held to the CPU oracle at <= 1e-3 by tests/test_gpu_parity.py) on the same noise",
-                                   "fp32_first_run_s_incl_setup": t32}
-            res["bf16_vs_fp32_rel_err"] = res["bf16_vs_fp32"]["rel_l2"]
-            del net32, y32
-            torch.cuda.empty_cache()
-        if world == 1 and a.config == "c2" and not a.no_other_workloads:
-            res["other_workloads"] = other_workloads(a)
-        if world == 1 and not a.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(cfg, a.length, nfe, value)
-            res["gpu_over_cpu"] = res["cpu_baseline"]["gpu_over_cpu_same_workload"]
-            if "config1" in res["cpu_baseline"]:
-                g1 = gpu_config1(device)
-                res["cpu_baseline"]["config1"]["gpu_hip_fp32"] = g1
-                best = max(v["waveforms_per_s"] for key, v in res["cpu_baseline"]["config1"].items() if key.startswith("threads_"))
-                res["cpu_baseline"]["config1"]["gpu_over_cpu"] = g1["waveforms_per_s"] / best      # against the FASTER of the two thread counts
+                t32 = time.perf_counter() - t1
+                if full:
+                    t1 = time.perf_counter()
+                    y32 = sampler(n32, fn=diff.denoise_fn, net=net32, sigmas=sigmas, **extra32)
+                    torch.cuda.synchronize()
+                    t32b = time.perf_counter() - t1
+                    res["fp32_mode_ms_per_step"] = t32b * 1e3
+                    res["fp32_mode"] = {"ms_per_step": t32b * 1e3, "value": nb * a.length / t32b, "unit": res["unit"], "waveforms_per_s": nb / t32b, "batch": nb,
+                                        "note": "same workload in the fp32 (parity-grade, exact-fp32 MFMA) mode: one graph-replayed sampler run after the capturing one"}
+                    # the split-bf16 mode (ADF_DTYPE_F32X3: fp32 storage, bf16 hi + lo operands, three bf16 MFMAs per product) on the same workload: the
+                    # in-tolerance mode meant to be USED (tests/test_gpu_parity.py::test_config2_full_sampler_fp32_vs_oracle holds it to the oracle at 1e-3)
+                    netx = make_net("f32x3")
+                    netx.load_state_dict(make_weights())
+                    netx = netx.to(device)
+                    yx = sampler(n32, fn=diff.denoise_fn, net=netx, sigmas=sigmas, **extra32)
+                    torch.cuda.synchronize()
+                    t1 = time.perf_counter()
+                    yx = sampler(n32, fn=diff.denoise_fn, net=netx, sigmas=sigmas, **extra32)
+                    torch.cuda.synchronize()
+                    tx = time.perf_counter() - t1
+                    dx = yx.to(torch.float64) - y32.to(torch.float64)
+                    res["f32x3_mode_ms_per_step"] = tx * 1e3
+                    res["f32x3_mode"] = {"ms_per_step": tx * 1e3, "value": nb * a.length / tx, "unit": res["unit"], "waveforms_per_s": nb / tx, "batch": nb,
+                                         "vs_fp32_rel_l2": float(dx.norm() / y32.to(torch.float64).norm()),
+                                         "vs_fp32_max_abs_over_max": float(dx.abs().max() / y32.abs().max()),
+                                         "note": "same workload in the split-bf16 mode (fp32 storage; every GEMM operand as bf16 hi + lo, 3 bf16 MFMAs per product, fp32 "
+                                                 "accumulation); deviation from the exact-fp32 mode over the whole 99-evaluation sampler on all waveforms"}
+                    del netx, yx
+                y16 = out[:nb].to(torch.float64)
+                d = y16 - y32.to(torch.float64)
+                res["bf16_vs_fp32"] = {"waveforms": nb, "rel_l2": float(d.norm() / y32.to(torch.float64).norm()),
+                                       "max_abs_over_max": float(d.abs().max() / y32.abs().max()),
+                                       "note": "bf16 run (the timed one) against the fp32 mode (held to the CPU oracle at <= 1e-3 by tests/test_gpu_parity.py) on the same noise",
+                                       "fp32_first_run_s_incl_setup": t32}
+                res["bf16_vs_fp32_rel_err"] = res["bf16_vs_fp32"]["rel_l2"]
+                del net32, y32
+                torch.cuda.empty_cache()
+            if world == 1 and a.config == "c2" and not a.no_other_workloads:
+                res["other_workloads"] = other_workloads(a)
+            if world == 1 and not a.no_cpu_baseline:
+                res["cpu_baseline"] = cpu_baseline(cfg, a.length, nfe, value)
+                res["gpu_over_cpu"] = res["cpu_baseline"]["gpu_over_cpu_same_workload"]
+                if "config1" in res["cpu_baseline"]:
+                    g1 = gpu_config1(device)
+                    res["cpu_baseline"]["config1"]["gpu_hip_fp32"] = g1
+                    best = max(v["waveforms_per_s"] for key, v in res["cpu_baseline"]["config1"].items() if key.startswith("threads_"))
+                    res["cpu_baseline"]["config1"]["gpu_over_cpu"] = g1["waveforms_per_s"] / best      # against the FASTER of the two thread counts
         print(json.dumps(res))
     if world > 1:
         dist.barrier()

@@ -93,6 +93,44 @@ def _json_lines(text):
     return [l for l in text.splitlines() if l.startswith("{")]
 
 
+def test_bench_dump_outputs_repeat_and_stay_within_budget(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the timed path returned in its last step as DIR/samples.npy (float32); two runs with the same
+    arguments write the same array (rehearsed with `--mock-device`: the stand-in step over the seeded noise).  An output beyond 64 MB is cut
+    to a fixed, seeded sample of whole rows."""
+    import importlib.util
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    bench = os.path.join(root, "bench.py")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    got = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, bench, "--gpus", "1", "--steps", "3", "--warmup", "1", "--mock-device", "--batch", "3", "--length", "128",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, env=env, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads(_json_lines(r.stdout)[-1])
+        assert j["steps"] == 3 and j["ms_per_step"] > 0
+        x = np.load(d / "samples.npy")
+        assert x.dtype == np.float32 and x.shape == (3, 1, 128)
+        got.append(x)
+    assert np.array_equal(got[0], got[1])
+    assert np.array_equal(got[0], torch.tanh(generate_noise(0, 3, 128) * 0.5).numpy())
+    spec = importlib.util.spec_from_file_location("bench_mod", bench)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert not mod.parse([]).full and mod.parse([]).dump_outputs is None
+    big = torch.arange(80, dtype=torch.float32)[:, None, None].expand(80, 1, 1 << 18)          # 80 MB
+    for run in range(2):
+        mod.dump_outputs(str(tmp_path / f"big{run}"), big)
+    a, b = np.load(tmp_path / "big0" / "samples.npy"), np.load(tmp_path / "big1" / "samples.npy")
+    assert a.nbytes <= mod.DUMP_LIMIT_BYTES and a.shape == (64, 1, 1 << 18) and np.array_equal(a, b)
+    rows = a[:, 0, 0]
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, np.broadcast_to(rows[:, None, None], a.shape))
+
+
 @pytest.mark.parametrize("how", ["torchrun", "self_launch"])
 def test_bench_rank_path_prints_one_line_from_rank_0(how):
     """bench.py's rank path (rendezvous on 127.0.0.1, index-keyed noise slices, fences, MAX over ranks, ONE all-gather, rank 0

@@ -1,6 +1,6 @@
 """Per-launch table of one network pass: the launcher's route lines (ADF_GEMM_TRACE=1, stderr) matched in order with the
 conv_gemm rows of a rocprofv3 kernel trace.
-usage (GPU box):  ADF_GEMM_TRACE=1 rocprofv3 --kernel-trace --output-format csv -d /tmp/lt -- python3 bench.py --steps 1 --warmup 0 \
+usage (GPU box):  ADF_GEMM_TRACE=1 rocprofv3 --kernel-trace --output-format csv -d /tmp/lt -- python3 bench.py --full --steps 1 --warmup 0 \
                       --num-steps 2 --no-graph --no-cpu-baseline 2> /tmp/lt.err ;  python3 tools/layer_table.py /tmp/lt /tmp/lt.err"""
 import csv, glob, re, sys
 trace = glob.glob(f"{sys.argv[1]}/*/*kernel_trace.csv")[0]
