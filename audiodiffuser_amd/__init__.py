@@ -1,6 +1,7 @@
 """MI355X-native EDM sampling hot path of AudioDiffuser.
 
-Plugin surface (hydra ``_target_`` s): ``audiodiffuser_amd.UNet1dBase`` / ``audiodiffuser_amd.WaveNetNoise`` (model.net),
+Plugin surface (hydra ``_target_`` s): ``audiodiffuser_amd.UNet1dBase`` / ``audiodiffuser_amd.WaveNetNoise`` / ``audiodiffuser_amd.UNetModel`` /
+``audiodiffuser_amd.UNet2dBase`` (model.net),
 ``audiodiffuser_amd.EluDiffusion`` (model.diffusion), ``audiodiffuser_amd.EDMSampler`` /
 ``EDMAlphaSampler`` / ``DPMSampler`` / ``DPM2Sampler`` / ``DPM2MSampler`` / ``ADPM2Sampler`` / ``ADPMPP2SSampler`` / ``LMSSampler`` / ``UniPCSampler`` (model.sampler), ``audiodiffuser_amd.KarrasSchedule``
 (model.noise_scheduler).
@@ -12,5 +13,7 @@ from .net import UNet1dBase  # noqa: F401
 from .wavenet import WaveNetNoise  # noqa: F401
 from .adm import UNetModel  # noqa: F401
 from .adm_config import ADMConfig, config_c4, config_c4_small  # noqa: F401
+from .unet2d import UNet2dBase  # noqa: F401
+from .unet2d_config import UNet2dConfig  # noqa: F401
 from .diffusion import EluDiffusion  # noqa: F401
 from .samplers import EDMSampler, EDMAlphaSampler, DPMSampler, DPM2Sampler, DPM2MSampler, ADPM2Sampler, ADPMPP2SSampler, LMSSampler, UniPCSampler  # noqa: F401

@@ -66,6 +66,22 @@ class AdfAdmConfig(C.Structure):
                 ("resblock_updown", C.c_int32), ("use_new_attention_order", C.c_int32), ("num_classes", C.c_int32), ("dtype", C.c_int32)]
 
 
+ADF_U2D_MAX_LEVELS, ADF_U2D_MAX_INIT_KERNELS = 8, 4
+
+
+class AdfUNet2dConfig(C.Structure):
+    """``adf_unet2d_config`` of include/audiodiffuser_amd.h."""
+    _fields_ = [("ff_mult", C.c_double),
+                ("dim", C.c_int32), ("cond_dim", C.c_int32), ("channels", C.c_int32), ("channels_out", C.c_int32), ("num_classes", C.c_int32),
+                ("n_levels", C.c_int32), ("dim_mults", C.c_int32 * ADF_U2D_MAX_LEVELS),
+                ("layer_attns", C.c_int32 * ADF_U2D_MAX_LEVELS), ("layer_cross_attns", C.c_int32 * ADF_U2D_MAX_LEVELS),
+                ("num_resnet_blocks", C.c_int32), ("resnet_groups", C.c_int32), ("attn_heads", C.c_int32),
+                ("layer_attns_depth", C.c_int32), ("layer_mid_attns_depth", C.c_int32), ("attend_at_middle", C.c_int32),
+                ("n_init_kernels", C.c_int32), ("init_kernel_sizes", C.c_int32 * ADF_U2D_MAX_INIT_KERNELS),
+                ("learned_sinu_pos_emb_dim", C.c_int32), ("num_time_tokens", C.c_int32),
+                ("scale_skip_connection", C.c_int32), ("final_resnet_block", C.c_int32), ("dtype", C.c_int32)]
+
+
 class AdfRunCounters(C.Structure):
     """``adf_run_counters`` of include/audiodiffuser_amd.h."""
     _fields_ = [("sampler_runs", C.c_int64), ("sampler_evals", C.c_int64), ("graph_captures", C.c_int64),
@@ -73,7 +89,7 @@ class AdfRunCounters(C.Structure):
 
 
 FLAG_NEAREST_UPSAMPLE = 2  # ADF_FLAG_NEAREST_UPSAMPLE
-ABI_VERSION = 5          # ADF_ABI_VERSION of the header this binding was written against
+ABI_VERSION = 6          # ADF_ABI_VERSION of the header this binding was written against
 
 EXPORTS = {
     # name: (restype, argtypes)
@@ -82,6 +98,7 @@ EXPORTS = {
     "adf_create": (C.c_int, [C.POINTER(AdfNetConfig), C.POINTER(C.c_void_p)]),
     "adf_wavenet_create": (C.c_int, [C.POINTER(AdfWaveNetConfig), C.POINTER(C.c_void_p)]),
     "adf_adm_create": (C.c_int, [C.POINTER(AdfAdmConfig), C.POINTER(C.c_void_p)]),
+    "adf_unet2d_create": (C.c_int, [C.POINTER(AdfUNet2dConfig), C.POINTER(C.c_void_p)]),
     "adf_set_image_shape": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "adf_set_dynamic_threshold": (C.c_int, [C.c_void_p, C.c_float]),
     "adf_destroy": (None, [C.c_void_p]),
@@ -178,6 +195,29 @@ def make_adm_config(cfg, dtype: int) -> AdfAdmConfig:
     c.use_scale_shift_norm, c.resblock_updown = int(cfg.use_scale_shift_norm), int(cfg.resblock_updown)
     c.use_new_attention_order = int(cfg.use_new_attention_order)
     c.num_classes = int(cfg.num_classes) if cfg.num_classes is not None else 0
+    c.dtype = dtype
+    return c
+
+
+def make_unet2d_config(cfg, dtype: int) -> AdfUNet2dConfig:
+    """From an ``audiodiffuser_amd.unet2d_config.UNet2dConfig``."""
+    n = len(cfg.dim_mults)
+    if n > ADF_U2D_MAX_LEVELS or len(cfg.init_cross_embed_kernel_sizes) > ADF_U2D_MAX_INIT_KERNELS:
+        raise ValueError("too many levels / cross-embed kernel sizes")
+    c = AdfUNet2dConfig()
+    c.ff_mult = float(cfg.ff_mult)
+    c.dim, c.cond_dim, c.channels, c.channels_out, c.num_classes = cfg.dim, cfg.cdim, cfg.channels, cfg.out_channels, int(cfg.num_classes)
+    c.n_levels = n
+    for i in range(n):
+        c.dim_mults[i], c.layer_attns[i], c.layer_cross_attns[i] = int(cfg.dim_mults[i]), int(cfg.layer_attns[i]), int(cfg.layer_cross_attns[i])
+    c.num_resnet_blocks, c.resnet_groups, c.attn_heads = cfg.num_resnet_blocks, cfg.resnet_groups, cfg.attn_heads
+    c.layer_attns_depth, c.layer_mid_attns_depth, c.attend_at_middle = cfg.layer_attns_depth, cfg.layer_mid_attns_depth, int(cfg.attend_at_middle)
+    ks = sorted(cfg.init_cross_embed_kernel_sizes)
+    c.n_init_kernels = len(ks)
+    for i, k in enumerate(ks):
+        c.init_kernel_sizes[i] = int(k)
+    c.learned_sinu_pos_emb_dim, c.num_time_tokens = cfg.learned_sinu_pos_emb_dim, cfg.num_time_tokens
+    c.scale_skip_connection, c.final_resnet_block = int(cfg.scale_skip_connection), int(cfg.final_resnet_block)
     c.dtype = dtype
     return c
 

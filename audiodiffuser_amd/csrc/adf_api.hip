@@ -31,7 +31,13 @@ int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out) {
         if (a.H % f || a.W % f || ((a.H / f) * (a.W / f)) % 64)
             return fail(h, "UNetModel: H and W must be multiples of 2^(levels-1) and the coarsest level a multiple of 64 pixels");
     }
-    const std::tuple<int, int, int> pkey{B, L, h->adm ? h->adm->H : 0};
+    if (h->u2d) {
+        const U2dW& u = *h->u2d;
+        const int f = 1 << u.cfg.n_levels;
+        if (u.H < 1 || u.W < 1 || (long long)u.H * u.W != L) return fail(h, "UNet2dBase: call adf_set_image_shape(H, W) with H * W equal to the length argument first");
+        if (u.H % f || u.W % f) return fail(h, "UNet2dBase: H and W must be multiples of 2^levels");
+    }
+    const std::tuple<int, int, int> pkey{B, L, h->adm ? h->adm->H : (h->u2d ? h->u2d->H : 0)};
     auto it = h->plans.find(pkey);
     if (it != h->plans.end()) { *out = it->second; h->last_plan = it->second; it->second->last_use = ++h->use_clock; return 0; }
     Plan* p = new Plan();
@@ -164,9 +170,57 @@ int adf_adm_create(const adf_adm_config* cfg, adf_handle** out) {
     return 0;
 }
 
+int adf_unet2d_create(const adf_unet2d_config* cfg, adf_handle** out) {
+    if (!cfg || !out) { g_create_error = "adf_unet2d_create: null argument"; return 1; }
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "adf_unet2d_create: no HIP device available"; return 1; }
+    const adf_unet2d_config& c = *cfg;
+    auto bad = [](const char* m) { g_create_error = std::string("adf_unet2d_create: ") + m; return 1; };
+    if (c.dtype != ADF_DTYPE_F32) return bad("only the exact-fp32 mode (ADF_DTYPE_F32) is built for this net");
+    if (c.n_levels < 1 || c.n_levels > ADF_U2D_MAX_LEVELS || c.num_resnet_blocks < 1) return bad("bad level / block counts");
+    if (c.n_init_kernels < 1 || c.n_init_kernels > ADF_U2D_MAX_INIT_KERNELS) return bad("1 to 4 cross-embed kernel sizes");
+    if (c.channels < 1 || c.channels_out < 1 || c.channels_out > 4) return bad("channels >= 1, 1 <= channels_out <= 4");
+    if (c.dim % 32 || c.dim < 32 || c.dim > 1024 || c.cond_dim < 1 || c.cond_dim > 512 || c.resnet_groups < 1 || c.attn_heads < 1) return bad("bad widths");
+    if (c.num_classes < 0 || (c.num_classes > 0 && (c.cond_dim != c.dim || c.dim > 512))) return bad("class conditioning needs cond_dim == dim <= 512");
+    if (c.learned_sinu_pos_emb_dim < 2 || c.learned_sinu_pos_emb_dim % 2 || c.num_time_tokens < 1) return bad("bad time embedding widths");
+    if (c.layer_attns_depth < 1 || c.layer_mid_attns_depth < 1 || !(c.ff_mult > 0.0)) return bad("bad transformer settings");
+    for (int i = 0; i < c.n_levels; ++i) {
+        const int w = c.dim * c.dim_mults[i];
+        if (c.dim_mults[i] < 1 || w > 512 || w % c.resnet_groups) return bad("level widths must be at most 512 (a skip concat feeds a conv of at most 1024 channels) and multiples of resnet_groups");
+        if (c.layer_attns[i] || c.attend_at_middle) {
+            if (w % c.attn_heads) return bad("attention widths must divide into the heads");
+        }
+    }
+    for (int i = 0; i < c.n_init_kernels; ++i)
+        if (c.init_kernel_sizes[i] < 1 || !(c.init_kernel_sizes[i] & 1) || (i && c.init_kernel_sizes[i] < c.init_kernel_sizes[i - 1])) return bad("cross-embed kernel sizes must be odd and sorted");
+    adf_handle* h = new adf_handle();
+    memset(&h->cfg, 0, sizeof(h->cfg));
+    // the fields of the U-Net config the shared plan / sampler code reads (time embedding width 4 * channels = 4 * cond_dim; label width = dim)
+    h->cfg.in_channels = c.channels; h->cfg.out_channels = c.channels_out; h->cfg.stride = 1; h->cfg.num_layers = 0;
+    h->cfg.channels = c.cond_dim; h->cfg.dtype = c.dtype; h->cfg.resnet_groups = c.resnet_groups; h->cfg.num_classes = c.num_classes;
+    if (hipGetDevice(&h->device) != hipSuccess) { g_create_error = "adf_unet2d_create: hipGetDevice failed"; delete h; return 1; }
+    h->bf16 = false;
+    h->esz = 4;
+    h->kc = kRowBytes / h->esz;
+    h->u2d = new U2dW();
+    U2dW& u = *h->u2d;
+    u.cfg = c;
+    u.init_dim = c.dim; u.tcd = 4 * c.cond_dim;
+    // CrossEmbedLayer's split of init_dim over the sorted kernel sizes (:268-272): init_dim / 2, / 4, ..., the remainder to the largest
+    for (int i = 0; i + 1 < c.n_init_kernels; ++i) u.ce_off[i + 1] = u.ce_off[i] + (c.dim >> (i + 1));
+    u.ce_off[c.n_init_kernels] = c.dim;
+    for (int i = 0; i < c.n_init_kernels; ++i)
+        if (u.ce_off[i + 1] - u.ce_off[i] < 4 || (u.ce_off[i + 1] - u.ce_off[i]) % 4) { g_create_error = "adf_unet2d_create: every cross-embed slice must be a multiple of 4 channels"; adf_destroy(h); return 1; }
+    if (u2d_build_weights(h)) { g_create_error = h->err; adf_destroy(h); return 1; }
+    *out = h;
+    return 0;
+}
+
 int adf_set_image_shape(adf_handle* h, int H, int W) {
-    if (!h || !h->adm) return h ? fail(h, "adf_set_image_shape: not a UNetModel handle") : 1;
+    if (!h || (!h->adm && !h->u2d)) return h ? fail(h, "adf_set_image_shape: not a UNetModel / UNet2dBase handle") : 1;
     if (H < 1 || W < 1) return fail(h, "adf_set_image_shape: bad shape");
+    if (h->u2d) { h->u2d->H = H; h->u2d->W = W; return 0; }
     h->adm->H = H; h->adm->W = W;
     return 0;
 }
@@ -182,6 +236,7 @@ void adf_destroy(adf_handle* h) {
     if (h->gstream) (void)hipStreamDestroy(h->gstream);
     delete h->wn;
     delete h->adm;
+    delete h->u2d;
     delete h;
 }
 
@@ -209,6 +264,10 @@ int adf_load_weight(adf_handle* h, const char* name, const float* dev, int64_t n
         if (const char* e = launch_permute_qkv_rows(dev, (float*)sl.dst, sl.f, sl.cout / (3 * sl.f), 1, s)) return fail(h, e);
     } else if (sl.kind == 4) {               // qkv weight: permute the rows into a scratch copy, then pack that
         if (const char* e = launch_permute_qkv_rows(dev, (float*)sl.frag, sl.f, sl.cout / (3 * sl.f), sl.cin, s)) return fail(h, e);
+        if (const char* e = launch_pack_weight((const float*)sl.frag, sl.dst, h->gemm_dtype(), 0, sl.cout, sl.cin, sl.K, 0, sl.n_offset, sl.n_pad, sl.nchunk, s))
+            return fail(h, e);
+    } else if (sl.kind == 6 && h->u2d) {     // UNet2dBase: a load-time transform into an fp32 scratch copy (adf_unet2d.h), then the usual packing
+        if (const char* e = launch_u2d_weight_transform(dev, (float*)sl.frag, sl.xmode, sl.cout, sl.cin, sl.K, sl.xc0, sl.xscale, s)) return fail(h, e);
         if (const char* e = launch_pack_weight((const float*)sl.frag, sl.dst, h->gemm_dtype(), 0, sl.cout, sl.cin, sl.K, 0, sl.n_offset, sl.n_pad, sl.nchunk, s))
             return fail(h, e);
     } else {
@@ -275,7 +334,7 @@ int adf_set_condition(adf_handle* h, const int64_t* classes_dev, int B, int null
         return fail(h, e);
     // class part of every FiLM projection: columns [tdim, tdim + cdim) of the concatenated weight, no bias (it is in the time part)
     // (not for the ADM net: its embeddings are ADDED before the SiLU of emb_layers, unet2d_oai.py:621-623, so nothing separates)
-    if (!h->adm)
+    if (!h->adm && !h->u2d)      // (nor for UNet2dBase: t + label embedding, then each block's SiLU -> Linear, unet2d.py:902-908)
         if (const char* e = launch_film(h->cond_emb, h->cdim, h->film_w, 4 * c.channels + h->cdim, 4 * c.channels, nullptr, h->cond_film, B + 1,
                                         h->film_total, s))
             return fail(h, e);
@@ -403,13 +462,18 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
             if (const char* e = launch_adm_time_embed(p->coef_all + 1, 4, n_eval, am.cfg.model_channels, am.t_w1, am.t_b1, am.t_w2, am.t_b2,
                                                       4 * am.cfg.model_channels, p->temb_all, st))
                 return fail(h, e);
+        } else if (h->u2d) {
+            const U2dW& u = *h->u2d;
+            if (const char* e = launch_u2d_time_embed(p->coef_all + 1, 4, n_eval, u.fourier, u.cfg.learned_sinu_pos_emb_dim / 2, u.t_w1, u.t_b1, u.t_w2, u.t_b2,
+                                                      u.tcd, p->temb_all, st))
+                return fail(h, e);
         } else {
             TimeEmbedArgs te;
             te.t = p->coef_all + 1; te.t_stride = 4; te.nb = n_eval; te.ch = cfg.channels;
             te.fourier = h->fourier; te.w1 = h->t_w1; te.b1 = h->t_b1; te.w2 = h->t_w2; te.b2 = h->t_b2; te.temb = p->temb_all;
             if (const char* e = launch_time_embed(te, st)) return fail(h, e);
         }
-        if (h->adm && h->cdim > 0) return 0;       // per-sample FiLM rows (time + class embedding): projected inside each pass
+        if ((h->adm || h->u2d) && h->cdim > 0) return 0;       // per-sample FiLM rows (time + class embedding): projected inside each pass
         if (const char* e = launch_film(p->temb_all, 4 * cfg.channels, h->film_w, 4 * cfg.channels + h->cdim, 0, h->film_b, p->film_all, n_eval,
                                         h->film_total, st))
             return fail(h, e);

@@ -4,6 +4,7 @@
 //   adf_net_unet1d.hip     UNet1dBase: registry + walk (unet1d.py:771-816)
 //   adf_net_wavenet.hip    WaveNetNoise (wavenet.py:153-180)
 //   adf_net_adm.hip        ADM UNetModel (unet2d_oai.py:382-635)
+//   adf_net_unet2d.hip     Imagen-style UNet2dBase (unet2d.py:622-972), exact fp32
 //   adf_sampler.hip        denoise wrappers and the sampler state machines (sampler_edm.py, stochastic_sampler_edm.py)
 //   adf_bench_replay.hip   adf_bench_* instrumentation
 #pragma once
@@ -12,6 +13,7 @@
 #include "adf_kernels.h"
 #include "adf_wavenet.h"
 #include "adf_conv2d.h"
+#include "adf_unet2d.h"
 #include "adf_transformer.h"
 #include "adf_resblock_small.h"
 #include "adf_resblock_split.h"
@@ -62,6 +64,7 @@ struct Slot {
     int64_t numel = 0;
     bool loaded = false;
     int cout = 0, cin = 0, K = 0, f = 0, n_offset = 0, n_pad = 0, nchunk = 0, taps = 0;
+    int xmode = 0, xc0 = 0; float xscale = 1.0f;   // kind 6 (UNet2dBase): launch_u2d_weight_transform(mode, c0, scale) into `frag`, then packed
 };
 
 struct Act { void* p = nullptr; int C = 0, L = 0; double* stats = nullptr; };
@@ -92,6 +95,38 @@ struct AdmW {
     float *out_gw = nullptr, *out_gb = nullptr, *out_w = nullptr, *out_b = nullptr;
     int input_ch = 0, final_ch = 0;
     int fg = 4;                          // channels per fine statistics group: gcd of every GroupNorm group size of the net (incl. the skip concats)
+};
+
+// Imagen-style UNet2dBase (unet2d.py:622-972): the module tree of the memory-efficient layout as data
+struct U2dRes {
+    int cin = 0, cout = 0, skip_c = 0, film_off = 0;   // skip_c: channels of the (scaled) skip half of the input (up blocks), 0 otherwise
+    float *g1w = nullptr, *g1b = nullptr, *g2w = nullptr, *g2b = nullptr;
+    ConvW c1, c2, res;
+    bool has_res = false, gca = false;
+    int gca_hid = 0;
+    float *gk_w = nullptr, *gk_b = nullptr, *gn0_w = nullptr, *gn0_b = nullptr, *gn2_w = nullptr, *gn2_b = nullptr;
+};
+struct U2dTrLayer { ConvW qkv, out, ff1, ff2; float *g0 = nullptr, *g3 = nullptr; };
+struct U2dTr { int c = 0, hid = 0, heads = 0; std::vector<U2dTrLayer> layers; float* norm_g = nullptr; };
+struct U2dLevel {
+    int din = 0, dout = 0;
+    ConvW down;                          // Downsample's 1x1 conv over unshuffled channels, packed as a 3x3 / stride-2 conv (slot kind 6)
+    std::vector<U2dRes> down_rb, up_rb;  // [0] = the block without a gate (ds_block.1 / us_block.0), then the gated ones
+    bool attn = false;
+    U2dTr down_tr, up_tr;
+    ConvW up;                            // PixelShuffleUpsample's 1x1 conv dout -> 4 din
+};
+struct U2dW {
+    adf_unet2d_config cfg;
+    int H = 0, W = 0;                    // image shape of the calls that follow (adf_set_image_shape)
+    int init_dim = 0, tcd = 0, fg = 4;
+    int ce_off[5] = {0};
+    float *ce_w[4] = {nullptr}, *ce_b[4] = {nullptr};
+    float *fourier = nullptr, *t_w1 = nullptr, *t_b1 = nullptr, *t_w2 = nullptr, *t_b2 = nullptr;
+    U2dRes init_rb, mid1, mid2, final_rb;
+    U2dTr mid_tr;
+    std::vector<U2dLevel> lv;
+    float *out_w = nullptr, *out_b = nullptr;
 };
 
 struct WnW {
@@ -178,6 +213,7 @@ struct adf_handle {
     Plan* last_plan = nullptr;
     WnW* wn = nullptr;                  // non-null: the handle is a WaveNetNoise (adf_wavenet_create), not a UNet1dBase
     AdmW* adm = nullptr;                // non-null: the handle is an ADM-style UNetModel (adf_adm_create)
+    U2dW* u2d = nullptr;                // non-null: the handle is an Imagen-style UNet2dBase (adf_unet2d_create)
     // graphs are captured and replayed on a library-owned stream (the caller's stream may be the legacy
     // default stream, which cannot be captured); it is fenced against the caller's stream with events
     hipStream_t gstream = nullptr;
@@ -609,11 +645,13 @@ struct FwdIO {
 
 int wn_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s);
 int adm_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s);
+int u2d_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s);
 
 int forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s);
 int wn_pack_weights(adf_handle* h, hipStream_t s);
 int wn_build_weights(adf_handle* h);
 int adm_build_weights(adf_handle* h);
+int u2d_build_weights(adf_handle* h);
 int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out);
 int cond_rows(adf_handle* h, int B, bool null_branch, FwdIO& io);
 int ensure_cfg_buffers(adf_handle* h, Plan* p);
@@ -633,7 +671,7 @@ struct SamplerCtx {
             FwdIO io;
             io.x = x; io.t = p->coef_all + (size_t)k * 4 + 1; io.t_stride = 4; io.nb = 1;
             io.coef = p->coef_all + (size_t)k * 4; io.coef_bstride = 0; io.x_noisy = x;
-            if (h->adm && h->cdim > 0) io.temb_pre = p->temb_all + (size_t)k * 4 * h->cfg.channels;
+            if ((h->adm || h->u2d) && h->cdim > 0) io.temb_pre = p->temb_all + (size_t)k * 4 * h->cfg.channels;
             else io.film_pre = p->film_all + (size_t)k * h->film_total;
             return denoise_io(h, p, io, out, s);
         }

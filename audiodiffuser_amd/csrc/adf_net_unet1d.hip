@@ -101,6 +101,7 @@ int forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
     if (!p->dry) ++h->ctr.net_passes;
     if (h->wn) return wn_forward(h, p, io, s);
     if (h->adm) return adm_forward(h, p, io, s);
+    if (h->u2d) return u2d_forward(h, p, io, s);
     const adf_net_config& c = h->cfg;
     Walker W{h, p, s};
     W.film2 = io.film2; W.film2_bstride = io.film2_bstride;

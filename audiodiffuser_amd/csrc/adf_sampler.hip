@@ -15,7 +15,7 @@ int cond_rows(adf_handle* h, int B, bool null_branch, FwdIO& io) {
     if (!h->cond_on || h->cond_B != B)
         return fail(h, "class-conditional network: call adf_set_condition with the labels of this batch first");
     io.null_cond = null_branch;
-    if (h->adm) return 0;            // the ADM net adds the class embedding to the time embedding before the FiLM projections (adm_forward)
+    if (h->adm || h->u2d) return 0;  // the ADM net (and UNet2dBase) adds the class embedding to the time embedding before the FiLM projections (adm_forward)
     if (null_branch) { io.film2 = h->cond_film + (size_t)B * h->film_total; io.film2_bstride = 0; }
     else { io.film2 = h->cond_film; io.film2_bstride = h->film_total; }
     return 0;

@@ -23,6 +23,7 @@ import torch.nn as nn
 from . import _lib
 from .adm_config import ADMConfig
 from .config import UNet1dConfig, WaveNetConfig
+from .unet2d_config import UNet2dConfig
 from .weights import param_specs
 
 _DTYPES = {"fp32": _lib.DTYPE_F32, "float32": _lib.DTYPE_F32, "bf16": _lib.DTYPE_BF16, "bfloat16": _lib.DTYPE_BF16,
@@ -47,6 +48,9 @@ class NativeHandle:
         elif isinstance(cfg, ADMConfig):
             c = _lib.make_adm_config(cfg, _DTYPES[dtype])
             rc, what = self.lib.adf_adm_create(C.byref(c), C.byref(h)), "adf_adm_create"
+        elif isinstance(cfg, UNet2dConfig):
+            c = _lib.make_unet2d_config(cfg, _DTYPES[dtype])
+            rc, what = self.lib.adf_unet2d_create(C.byref(c), C.byref(h)), "adf_unet2d_create"
         else:
             c = _lib.make_config(cfg, _DTYPES[dtype], flags)
             rc, what = self.lib.adf_create(C.byref(c), C.byref(h)), "adf_create"
@@ -111,11 +115,11 @@ class NativeHandle:
     def _length(self, x: torch.Tensor) -> int:
         """The C ABI's length argument: L for [B, C, L]; H * W for the 2-D U-Net's [B, C, H, W] (after telling the handle the shape)."""
         if x.ndim == 4:
-            if not isinstance(self.cfg, ADMConfig):
+            if not isinstance(self.cfg, (ADMConfig, UNet2dConfig)):
                 raise ValueError("a 4-D input needs the 2-D UNetModel")
             self.check(self.lib.adf_set_image_shape(self.h, int(x.shape[2]), int(x.shape[3])), "adf_set_image_shape")
             return int(x.shape[2] * x.shape[3])
-        if isinstance(self.cfg, ADMConfig):
+        if isinstance(self.cfg, (ADMConfig, UNet2dConfig)):
             raise ValueError("the 2-D UNetModel takes [B, C, H, W] inputs")
         return int(x.shape[-1])
 

@@ -16,6 +16,8 @@
  *                                     through the same entry points: adf_load_weight (the module's state_dict keys, incl. the
  *                                     custom WeightNorm's weight_g / weight_v, wavenet.py:15-55), adf_net_forward
  *                                     <- WaveNetNoise.forward (wavenet.py:169-180), adf_denoise / adf_sampler_run as above
+ *   adf_unet2d_create              <- UNet2dBase.__init__ (src/models/backbones/unet2d.py:622-876); adf_net_forward on that handle
+ *                                     <- UNet2dBase.forward (:879-972)
  *
  * Conventions
  *   - every function returns 0 on success, non-zero on failure; adf_last_error() gives the message.
@@ -45,8 +47,9 @@ extern "C" {
  * 3: adf_sampler_run(n_injected), adf_sampler_desc.reflow, adf_get_counters.
  * 4: ADF_FLAG_NEAREST_UPSAMPLE (adf_net_config.flags bit 1; state-dict keys ...upsample.2.weight / .bias), WaveNetNoise in bf16 at 64 / 128
  *    residual channels, adf_debug_tap on a WaveNet handle keeps every layer while all of them fit 512 MiB (256 MiB before).
- * 5: ADF_DTYPE_F32X3 (a third value of adf_net_config.dtype: fp32 storage, every GEMM operand split into bf16 hi + lo, three bf16 MFMAs per product). */
-#define ADF_ABI_VERSION 5
+ * 5: ADF_DTYPE_F32X3 (a third value of adf_net_config.dtype: fp32 storage, every GEMM operand split into bf16 hi + lo, three bf16 MFMAs per product).
+ * 6: adf_unet2d_config / adf_unet2d_create (the Imagen-style UNet2dBase, exact fp32). */
+#define ADF_ABI_VERSION 6
 int adf_abi_version(void);
 
 #define ADF_MAX_LAYERS 12
@@ -124,6 +127,24 @@ typedef struct adf_adm_config {
     int32_t dtype;
 } adf_adm_config;
 
+/* Hyper-parameters of the Imagen-style UNet2dBase (unet2d.py:623-667) in the layout the device runs: memory_efficient, cross-embed initial conv,
+ * global-context gates, pixel-shuffle upsampling, no text / condition encoder.  init_kernel_sizes: the cross-embed kernel sizes sorted ascending
+ * (all odd); layer_cross_attns only decides which resnet blocks carry a (never run) cross_attn module in the state dict. */
+#define ADF_U2D_MAX_LEVELS 8
+#define ADF_U2D_MAX_INIT_KERNELS 4
+typedef struct adf_unet2d_config {
+    double ff_mult;
+    int32_t dim, cond_dim, channels, channels_out, num_classes;
+    int32_t n_levels; int32_t dim_mults[ADF_U2D_MAX_LEVELS];
+    int32_t layer_attns[ADF_U2D_MAX_LEVELS]; int32_t layer_cross_attns[ADF_U2D_MAX_LEVELS];
+    int32_t num_resnet_blocks, resnet_groups, attn_heads;
+    int32_t layer_attns_depth, layer_mid_attns_depth, attend_at_middle;
+    int32_t n_init_kernels; int32_t init_kernel_sizes[ADF_U2D_MAX_INIT_KERNELS];
+    int32_t learned_sinu_pos_emb_dim, num_time_tokens;
+    int32_t scale_skip_connection, final_resnet_block;
+    int32_t dtype;                          /* ADF_DTYPE_F32 only */
+} adf_unet2d_config;
+
 typedef struct adf_handle adf_handle;
 
 int adf_create(const adf_net_config* cfg, adf_handle** out);
@@ -132,6 +153,10 @@ int adf_create(const adf_net_config* cfg, adf_handle** out);
  * attention order, unconditional (BASELINE config 4) or class-conditional.  Debug taps: "input_blocks.<i>", "middle_block",
  * "output_blocks.<i>" (the outputs of the reference's blocks). */
 int adf_adm_create(const adf_adm_config* cfg, adf_handle** out);
+/* A UNet2dBase handle: the same 2-D conventions as a UNetModel handle (adf_set_image_shape first; H and W multiples of 2^n_levels).
+ * forward(x, time = c_noise), optionally class-conditional (adf_set_condition).  Debug taps: "init_conv", "init_resnet_block", "downs.<i>",
+ * "mid_block", "ups.<i>", "final_res_block" (the module outputs the reference's fixtures hold) and every stored intermediate. */
+int adf_unet2d_create(const adf_unet2d_config* cfg, adf_handle** out);
 int adf_set_image_shape(adf_handle* h, int H, int W);
 
 /* Clipping of every denoiser evaluation from here on (adf_denoise, adf_sampler_run): 0 = clamp to [-1, 1] (the default), q in (0, 1] = the dynamic

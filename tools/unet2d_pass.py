@@ -1,0 +1,42 @@
+"""Wall time of the shipped sc09 UNet2dBase (exact fp32) on the device: ms per forward at [B, 2, 256, 128] and ms per 50-step DPM run
+(DPMSampler order 3 multistep, the sc09 eval setting; graph-replayed).  Usage: unet2d_pass.py [B] [repeats]; prints one JSON line."""
+import json, os, sys
+import torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import audiodiffuser_amd as A
+
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
+R = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+dev = torch.device("cuda", 0)
+torch.manual_seed(0)
+net = A.UNet2dBase(**vars(A.unet2d_config.config_sc09(0)), memory_efficient=True).to(dev)
+with torch.no_grad():
+    net.final_conv.weight.normal_(0.0, 0.02)                 # (zero-initialised in the reference: keep the output non-trivial)
+x = torch.randn(B, 2, 256, 128, device=dev) * 0.5
+t = torch.full((B,), 0.3, device=dev)
+
+
+def timed(fn, reps):
+    fn()                                                      # warm-up (workspace, code objects, graph capture)
+    torch.cuda.synchronize()
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    ms = []
+    for _ in range(reps):
+        ev[0].record()
+        fn()
+        ev[1].record()
+        torch.cuda.synchronize()
+        ms.append(ev[0].elapsed_time(ev[1]))
+    return sorted(ms)[len(ms) // 2], ms
+
+
+with torch.no_grad():
+    fwd_ms, fwd_all = timed(lambda: net(x, t), R)
+    diff = A.EluDiffusion(sigma_data=0.2)
+    sig = A.KarrasSchedule(0.002, 80.0, 7.0, 50)()
+    smp = A.DPMSampler(cond_scale=1.0, order=3, num_steps=50, multisteps=True, x0_pred=True, log_time_spacing=False, use_graph=True)
+    noise = torch.randn(B, 2, 256, 128, device=dev)
+    run_ms, run_all = timed(lambda: smp(noise, fn=diff.denoise_fn, net=net, sigmas=sig), max(1, R // 2))
+print(json.dumps({"net": "UNet2dBase sc09 (fp32)", "batch": B, "shape": [B, 2, 256, 128], "ms_per_forward": round(fwd_ms, 2),
+                  "ms_per_forward_all": [round(v, 2) for v in fwd_all], "ms_per_50step_dpm": round(run_ms, 1),
+                  "ms_per_50step_dpm_all": [round(v, 1) for v in run_all]}))
