@@ -2,18 +2,18 @@
 
 Plugin surface (hydra ``_target_`` s): ``audiodiffuser_amd.UNet1dBase`` / ``audiodiffuser_amd.WaveNetNoise`` / ``audiodiffuser_amd.UNetModel`` /
 ``audiodiffuser_amd.UNet2dBase`` (model.net),
-``audiodiffuser_amd.EluDiffusion`` (model.diffusion), ``audiodiffuser_amd.EDMSampler`` /
-``EDMAlphaSampler`` / ``DPMSampler`` / ``DPM2Sampler`` / ``DPM2MSampler`` / ``ADPM2Sampler`` / ``ADPMPP2SSampler`` / ``LMSSampler`` / ``UniPCSampler`` (model.sampler), ``audiodiffuser_amd.KarrasSchedule``
+``audiodiffuser_amd.EluDiffusion`` / ``VEDiffusion`` / ``VPDiffusion`` / ``VDiffusion`` (model.diffusion), ``audiodiffuser_amd.EDMSampler`` /
+``EDMAlphaSampler`` / ``DPMSampler`` / ``DPM2Sampler`` / ``DPM2MSampler`` / ``ADPM2Sampler`` / ``ADPMPP2SSampler`` / ``LMSSampler`` / ``UniPCSampler`` (model.sampler), ``audiodiffuser_amd.KarrasSchedule`` / ``VESchedule`` / ``VPSchedule`` / ``VSchedule`` / ``LinearSchedule`` / ``GeometricSchedule``
 (model.noise_scheduler).
 """
 from .config import UNet1dConfig, config_c1, config_c2, config_c3, config_tiny, config_tiny_cc, PRESETS  # noqa: F401
 from .config import WaveNetConfig, config_c5, config_c5_small  # noqa: F401
-from .scheduler import KarrasSchedule  # noqa: F401
+from .scheduler import KarrasSchedule, LinearSchedule, GeometricSchedule, VPSchedule, VESchedule, VSchedule  # noqa: F401
 from .net import UNet1dBase  # noqa: F401
 from .wavenet import WaveNetNoise  # noqa: F401
 from .adm import UNetModel  # noqa: F401
 from .adm_config import ADMConfig, config_c4, config_c4_small  # noqa: F401
 from .unet2d import UNet2dBase  # noqa: F401
 from .unet2d_config import UNet2dConfig  # noqa: F401
-from .diffusion import EluDiffusion  # noqa: F401
+from .diffusion import EluDiffusion, VEDiffusion, VPDiffusion, VDiffusion  # noqa: F401
 from .samplers import EDMSampler, EDMAlphaSampler, DPMSampler, DPM2Sampler, DPM2MSampler, ADPM2Sampler, ADPMPP2SSampler, LMSSampler, UniPCSampler  # noqa: F401

@@ -89,7 +89,8 @@ class AdfRunCounters(C.Structure):
 
 
 FLAG_NEAREST_UPSAMPLE = 2  # ADF_FLAG_NEAREST_UPSAMPLE
-ABI_VERSION = 6          # ADF_ABI_VERSION of the header this binding was written against
+PRECOND_EDM, PRECOND_VE, PRECOND_VP, PRECOND_V_EDM = 0, 1, 2, 3      # ADF_PRECOND_* (adf_set_preconditioning)
+ABI_VERSION = 7          # ADF_ABI_VERSION of the header this binding was written against
 
 EXPORTS = {
     # name: (restype, argtypes)
@@ -101,6 +102,8 @@ EXPORTS = {
     "adf_unet2d_create": (C.c_int, [C.POINTER(AdfUNet2dConfig), C.POINTER(C.c_void_p)]),
     "adf_set_image_shape": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "adf_set_dynamic_threshold": (C.c_int, [C.c_void_p, C.c_float]),
+    "adf_set_preconditioning": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]),
+    "adf_debug_coef_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "adf_destroy": (None, [C.c_void_p]),
     "adf_last_error": (C.c_char_p, [C.c_void_p]),
     "adf_num_weights": (C.c_int, [C.c_void_p]),

@@ -349,6 +349,27 @@ int adf_set_dynamic_threshold(adf_handle* h, float quantile) {
     return 0;
 }
 
+int adf_set_preconditioning(adf_handle* h, int kind, double beta_min, double beta_d, double M) {
+    if (!h) return 1;
+    Precond pc;
+    switch (kind) {
+        case ADF_PRECOND_EDM: pc.kind = ADF_PRECOND_KIND_EDM; break;
+        case ADF_PRECOND_VE: pc.kind = ADF_PRECOND_KIND_VE; break;
+        case ADF_PRECOND_V_EDM: pc.kind = ADF_PRECOND_KIND_V_EDM; break;
+        case ADF_PRECOND_VP:
+            if (!(beta_d != 0.0) || !std::isfinite(beta_min) || !std::isfinite(beta_d) || !std::isfinite(M))
+                return fail(h, "adf_set_preconditioning: ADF_PRECOND_VP needs finite beta_min, beta_d != 0 and M");
+            pc.kind = ADF_PRECOND_KIND_VP;
+            // the reference forms these in Python doubles; torch rounds each scalar operand to fp32 (diffusion.py:159-160, :165)
+            pc.beta_min2 = (float)(beta_min * beta_min); pc.two_beta_d = (float)(2.0 * beta_d);
+            pc.beta_min = (float)beta_min; pc.beta_d = (float)beta_d; pc.m_minus_1 = (float)(M - 1.0);
+            break;
+        default: return fail(h, "adf_set_preconditioning: unknown kind (ADF_PRECOND_EDM, _VE, _VP, _V_EDM)");
+    }
+    h->precond = pc;
+    return 0;
+}
+
 int adf_denoise(adf_handle* h, const float* x_noisy, const float* sigmas_dev, float sigma, float sigma_data, float* out, int B,
                 int L, void* stream) {
     ADF_ON_DEVICE(h);
@@ -357,7 +378,7 @@ int adf_denoise(adf_handle* h, const float* x_noisy, const float* sigmas_dev, fl
     if (get_plan(h, B, L, s, &p)) return 1;
     ++h->ctr.denoise_calls;
     if (!sigmas_dev) return denoise_scalar(h, p, x_noisy, sigma, sigma_data, out, s);
-    if (const char* e = launch_edm_coef(sigmas_dev, 0.f, B, sigma_data, p->coef, s)) return fail(h, e);
+    if (const char* e = launch_edm_coef(sigmas_dev, 0.f, B, h->precond_for(sigma_data), p->coef, s)) return fail(h, e);
     FwdIO io;
     io.x = x_noisy; io.t = p->coef + 1; io.t_stride = 4; io.nb = B;
     io.coef = p->coef; io.coef_bstride = 4; io.x_noisy = x_noisy;
@@ -385,6 +406,7 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
         if (!h->cond_on || h->cond_B != B) return fail(h, "class-conditional network: call adf_set_condition with the labels of this batch first");
         if (h->cond_scale != 1.0f && ensure_cfg_buffers(h, p)) return 1;
     }
+    if (h->unclipped() && !h->u2d && ensure_cfg_buffers(h, p)) return 1;     // unclipped estimate off UNet2dBase: raw pass + combine (denoise_io)
     if (h->dyn_q > 0.0f) {                               // buffers of the dynamic threshold: allocated before any capture starts
         if (ensure_cfg_buffers(h, p)) return 1;
         if (!p->dyn_scale) {
@@ -431,6 +453,7 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
         if (run_sampler(cc, &r0)) eval_sigmas.clear();     // a schedule the sampler rejects: the real pass below reports why
     }
     const int n_eval = (int)eval_sigmas.size();
+    p->pre_rows = n_eval;
     if (n_eval > p->pre_cap) {
         if (p->pre_cap) {
             (void)hipDeviceSynchronize();
@@ -451,7 +474,7 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
     auto sigma_table = [&](hipStream_t st) -> int {
         if (n_eval == 0) return 0;
         const adf_net_config& cfg = h->cfg;
-        if (const char* e = launch_edm_coef_list(eval_sigmas.data(), n_eval, desc->sigma_data, p->coef_all, st)) return fail(h, e);
+        if (const char* e = launch_edm_coef_list(eval_sigmas.data(), n_eval, h->precond_for(desc->sigma_data), p->coef_all, st)) return fail(h, e);
         if (h->wn) {
             const adf_wavenet_config& wc = h->wn->cfg;
             if (const char* e = launch_wn_step_embed(p->coef_all + 1, 4, n_eval, h->wn->fc1w, h->wn->fc1b, h->wn->fc2w, h->wn->fc2b, wc.dim_in,
@@ -506,6 +529,11 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
     key.push_back(h->cond_on ? 'c' : 'u');                   // the guidance branch structure is part of the captured graph
     key.append((const char*)&h->cond_scale, sizeof(float));
     key.append((const char*)&h->dyn_q, sizeof(float));        // the clipping of every evaluation is part of the captured graph
+    {                                                          // ... and so are the preconditioning formulas and their parameters
+        const Precond& pc = h->precond;
+        const float pk[6] = {(float)pc.kind, pc.beta_min2, pc.two_beta_d, pc.beta_min, pc.beta_d, pc.m_minus_1};
+        key.append((const char*)pk, sizeof(pk));
+    }
     auto it = std::find_if(p->graphs.begin(), p->graphs.end(), [&](const std::pair<std::string, hipGraphExec_t>& g) { return g.first == key; });
     if (it != p->graphs.end() && it != p->graphs.begin()) {      // most recently used first
         std::rotate(p->graphs.begin(), it, it + 1);
@@ -559,6 +587,17 @@ int adf_debug_dyn_threshold(adf_handle* h, float* x_dev, int B, long long per_sa
     (void)hipStreamSynchronize((hipStream_t)stream);
     dfree(h, sc, (size_t)B * 4);
     return e ? fail(h, e) : 0;
+}
+
+int adf_debug_coef_rows(adf_handle* h, float* out_dev, int max_rows, int* n_rows, void* stream) {
+    ADF_ON_DEVICE(h);
+    if (!h->last_plan || !h->last_plan->coef_all) return fail(h, "adf_debug_coef_rows: no sampler run yet");
+    const Plan* p = h->last_plan;
+    if (n_rows) *n_rows = p->pre_rows;
+    const int n = std::min(max_rows, p->pre_rows);
+    if (n > 0 && out_dev && hipMemcpyAsync(out_dev, p->coef_all, (size_t)n * 4 * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+        return fail(h, "adf_debug_coef_rows: copy failed");
+    return 0;
 }
 
 int adf_debug_tap_count(adf_handle* h) { return h->last_plan ? (int)h->last_plan->taps.size() : 0; }

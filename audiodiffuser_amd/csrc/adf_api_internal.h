@@ -152,6 +152,7 @@ struct Plan {
     // known on the host) instead of three launches per evaluation
     float *coef_all = nullptr, *temb_all = nullptr, *film_all = nullptr;
     int pre_cap = 0;
+    int pre_rows = 0;                                     // rows of coef_all the last sampler run filled (adf_debug_coef_rows)
     // sampler state (fp32 [B][C][L] each)
     float* sb[10] = {nullptr};
     float* noise_stage = nullptr; float* out_stage = nullptr; float* inj_stage = nullptr; size_t inj_cap = 0;
@@ -198,6 +199,9 @@ struct adf_handle {
     bool cond_on = false;
     int cond_B = 0;
     float cond_scale = 1.0f;
+    Precond precond;                                     // which diffusion class's rows every evaluation uses (adf_set_preconditioning); sigma_data is filled per call
+    Precond precond_for(float sigma_data) const { Precond pc = precond; pc.sigma_data = sigma_data; return pc; }
+    bool unclipped() const { return precond.kind == ADF_PRECOND_KIND_V_EDM; }      // VDiffusion(for_edm=True) returns v_to_x0 as it is (diffusion.py:326)
     float dyn_q = 0.0f;                                  // > 0: dynamic thresholding at this quantile instead of clamp(-1, 1) (adf_set_dynamic_threshold)
     long long* cond_classes = nullptr;  // [cond_B]
     float* cond_emb = nullptr;          // [cond_B + 1][cdim], last row = null embedding
@@ -636,7 +640,8 @@ struct Walker {
 struct FwdIO {
     const float* x = nullptr; float* out = nullptr;
     const float* t = nullptr; int t_stride = 0; int nb = 0;
-    const float* coef = nullptr; int coef_bstride = 0; int mode = 0; const float* x_noisy = nullptr;
+    const float* coef = nullptr; int coef_bstride = 0; const float* x_noisy = nullptr;
+    int mode = 0;                                          // 0: raw network output; 1: clamp(c_skip x_noisy + c_out F, -1, 1); 2: the same unclipped (UNet2dBase only)
     const float* film2 = nullptr; int film2_bstride = 0;   // class part of the FiLM projections (rows of adf_handle::cond_film)
     const float* film_pre = nullptr;                       // this evaluation's row of Plan::film_all: sigma embedding + FiLM already computed
     const float* temb_pre = nullptr;                       // this evaluation's row of Plan::temb_all (class-conditional ADM net: the FiLM rows are per sample)

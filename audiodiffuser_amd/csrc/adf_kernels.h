@@ -44,11 +44,19 @@ const char* launch_to_out(const void* h, const float* w, float* out, int dtype, 
                           int wl, int stride, int pad, int mode, const float* x_noisy, const float* coef,
                           int coef_bstride, hipStream_t s);
 
-// coef[b][4] = (c_in, c_noise, c_skip, c_out) from sigma (EluDiffusion.get_scale_weights).
-const char* launch_edm_coef(const float* sigmas_dev, float sigma_scalar, int nb, float sigma_data, float* coef,
+// Which formulas turn a sigma into its row (adf_set_preconditioning); the constants are rounded to fp32 from the doubles the reference holds them in
+// (torch rounds a Python scalar operand to the tensor's dtype): beta_min2 = beta_min ** 2, two_beta_d = 2 * beta_d, m_minus_1 = M - 1.
+enum { ADF_PRECOND_KIND_EDM = 0, ADF_PRECOND_KIND_VE = 1, ADF_PRECOND_KIND_VP = 2, ADF_PRECOND_KIND_V_EDM = 3 };
+struct Precond {
+    int kind = ADF_PRECOND_KIND_EDM;
+    float sigma_data = 1.0f;                                                      // EDM
+    float beta_min2 = 0.f, two_beta_d = 0.f, beta_min = 0.f, beta_d = 1.f, m_minus_1 = 0.f;   // VP
+};
+// coef[b][4] = (c_in, c_noise, c_skip, c_out) from sigma (get_scale_weights of the diffusion class `pc` names).
+const char* launch_edm_coef(const float* sigmas_dev, float sigma_scalar, int nb, const Precond& pc, float* coef,
                             hipStream_t s);
 // coef[i] for a host-side list of sigmas (values passed in the kernel arguments: usable inside a stream capture)
-const char* launch_edm_coef_list(const float* sigmas_host, int n, float sigma_data, float* coef, hipStream_t s);
+const char* launch_edm_coef_list(const float* sigmas_host, int n, const Precond& pc, float* coef, hipStream_t s);
 
 // Time embedding MLP: t[b] -> temb[b][4*ch];  t read as t[b*t_stride].
 struct TimeEmbedArgs {

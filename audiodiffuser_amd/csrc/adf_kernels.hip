@@ -1293,45 +1293,82 @@ const char* launch_to_out(const void* h, const float* w, float* out, int dtype, 
 }
 
 // =====================================================================================================
-// EDM preconditioning scalars (diffusion.py:232-241): coef[b] = (c_in, c_noise, c_skip, c_out)
+// Preconditioning scalars: coef[b] = (c_in, c_noise, c_skip, c_out) of one sigma, fp32 in the reference's order of operations
+// (diffusion.py: EluDiffusion :232-241, VEDiffusion :107-116, VPDiffusion :156-170, VDiffusion(for_edm=True) :310-313 + v_to_x0 :290).
+// Every operation of the new branches is rounded to fp32 on its own (through double and a cast, which the compiler cannot contract): torch rounds
+// sigma^2 before it adds 1, and at the low end of VPSchedule ln(1 + sigma^2) keeps three digits, so that rounding decides c_noise -- and with c_noise
+// in the hundreds one ulp of it is 1e-4 rad of the sinusoidal embedding's phase.  The EDM branch is compiled as it always was.
 // =====================================================================================================
-__global__ void edm_coef_kernel(const float* __restrict__ sigmas, float sigma_scalar, int nb, float sd, float* __restrict__ coef) {
+// ln / exp evaluated in double and rounded once: the correctly rounded fp32 value, which is what the reference's CPU library returns on every sigma of
+// the shipped schedules (the fixture's c_noise columns equal their rounded float64 values); the device's logf is one ulp off at sigma = 1808, and at
+// logsnr = -15 that ulp is a 1e-6 relative change of alpha_t.  (Each is rounded to fp32 where torch rounds: the sequence of fp32 operations is kept.)
+__device__ __forceinline__ float precond_log(float x) { return (float)log((double)x); }
+__device__ __forceinline__ float precond_exp(float x) { return (float)exp((double)x); }
+// sqrt and the quotient of two floats through double are correctly rounded whatever the compiler's fp32 sqrt / divide settings (53 >= 2 * 24 + 2 bits)
+__device__ __forceinline__ float precond_sqrt(float x) { return (float)sqrt((double)x); }
+__device__ __forceinline__ float precond_div(float a, float b) { return (float)((double)a / (double)b); }
+// a product of two floats is exact in double and a cast cannot be fused into the operation that follows: each of these is one fp32 rounding
+__device__ __forceinline__ float precond_mul(float a, float b) { return (float)((double)a * (double)b); }
+__device__ __forceinline__ float precond_add(float a, float b) { return (float)((double)a + (double)b); }
+__device__ __forceinline__ float precond_sigmoid(float x) { return precond_div(1.0f, precond_add(1.0f, precond_exp(-x))); }
+__device__ __forceinline__ void precond_row(const Precond& pc, float s, float* __restrict__ row) {
+    if (pc.kind == ADF_PRECOND_KIND_VE) {
+        row[0] = 1.0f;
+        row[1] = precond_log(precond_mul(0.5f, s));
+        row[2] = 1.0f;
+        row[3] = s;
+    } else if (pc.kind == ADF_PRECOND_KIND_VP) {
+        const float s2 = precond_mul(s, s);
+        const float l = precond_log(precond_add(1.0f, s2));
+        const float t = precond_div(precond_add(precond_sqrt(precond_add(pc.beta_min2, precond_mul(pc.two_beta_d, l))), -pc.beta_min), pc.beta_d);   // sigma_to_t :159-160
+        row[0] = precond_div(1.0f, precond_sqrt(precond_add(s2, 1.0f)));
+        row[1] = precond_mul(pc.m_minus_1, t);
+        row[2] = 1.0f;
+        row[3] = -s;
+    } else if (pc.kind == ADF_PRECOND_KIND_V_EDM) {
+        const float logsnr = precond_mul(-2.0f, precond_log(s));                 // sigma_to_logsnr :287-288
+        const float sigmat = precond_sqrt(precond_sigmoid(-logsnr)), alphat = precond_sqrt(precond_sigmoid(logsnr));
+        row[0] = alphat;                                                // x_noisy * alphat is the network input (:312)
+        row[1] = logsnr;
+        row[2] = precond_mul(alphat, alphat);                             // v_to_x0 multiplies the scaled input by alphat again
+        row[3] = -sigmat;
+    } else {
+        const float sd = pc.sigma_data;
+        const float s2 = s * s, d2 = sd * sd;
+        row[0] = 1.0f / sqrtf(s2 + d2);
+        row[1] = logf(s) * 0.25f;
+        row[2] = d2 / (s2 + d2);
+        row[3] = s * sd * (1.0f / sqrtf(d2 + s2));
+    }
+}
+
+__global__ void edm_coef_kernel(const float* __restrict__ sigmas, float sigma_scalar, int nb, const Precond pc, float* __restrict__ coef) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nb) return;
-    const float s = sigmas ? sigmas[b] : sigma_scalar;
-    const float s2 = s * s, d2 = sd * sd;
-    coef[b * 4 + 0] = 1.0f / sqrtf(s2 + d2);
-    coef[b * 4 + 1] = logf(s) * 0.25f;
-    coef[b * 4 + 2] = d2 / (s2 + d2);
-    coef[b * 4 + 3] = s * sd * (1.0f / sqrtf(d2 + s2));
+    precond_row(pc, sigmas ? sigmas[b] : sigma_scalar, coef + (size_t)b * 4);
 }
 
 // The same for a list of sigmas known on the host (the sigma of every denoiser evaluation of a sampler run): the values ride in
 // the kernel arguments (no host -> device copy inside a captured graph), 256 per launch.
 struct SigmaPack { float s[256]; };
-__global__ void edm_coef_pack_kernel(const SigmaPack pk, int n, float sd, float* __restrict__ coef) {
+__global__ void edm_coef_pack_kernel(const SigmaPack pk, int n, const Precond pc, float* __restrict__ coef) {
     const int b = threadIdx.x;
     if (b >= n) return;
-    const float s = pk.s[b];
-    const float s2 = s * s, d2 = sd * sd;
-    coef[b * 4 + 0] = 1.0f / sqrtf(s2 + d2);
-    coef[b * 4 + 1] = logf(s) * 0.25f;
-    coef[b * 4 + 2] = d2 / (s2 + d2);
-    coef[b * 4 + 3] = s * sd * (1.0f / sqrtf(d2 + s2));
+    precond_row(pc, pk.s[b], coef + (size_t)b * 4);
 }
-const char* launch_edm_coef_list(const float* sigmas_host, int n, float sigma_data, float* coef, hipStream_t s) {
+const char* launch_edm_coef_list(const float* sigmas_host, int n, const Precond& pc, float* coef, hipStream_t s) {
     for (int i0 = 0; i0 < n; i0 += 256) {
         SigmaPack pk;
         const int m = n - i0 < 256 ? n - i0 : 256;
         for (int i = 0; i < 256; ++i) pk.s[i] = i < m ? sigmas_host[i0 + i] : 1.0f;
-        hipLaunchKernelGGL(edm_coef_pack_kernel, dim3(1), dim3(256), 0, s, pk, m, sigma_data, coef + (size_t)i0 * 4);
+        hipLaunchKernelGGL(edm_coef_pack_kernel, dim3(1), dim3(256), 0, s, pk, m, pc, coef + (size_t)i0 * 4);
         if (hipGetLastError() != hipSuccess) return "edm_coef_list: launch failed";
     }
     return nullptr;
 }
 
-const char* launch_edm_coef(const float* sigmas_dev, float sigma_scalar, int nb, float sigma_data, float* coef, hipStream_t s) {
-    hipLaunchKernelGGL(edm_coef_kernel, dim3(ceil_div(nb, 64)), dim3(64), 0, s, sigmas_dev, sigma_scalar, nb, sigma_data, coef);
+const char* launch_edm_coef(const float* sigmas_dev, float sigma_scalar, int nb, const Precond& pc, float* coef, hipStream_t s) {
+    hipLaunchKernelGGL(edm_coef_kernel, dim3(ceil_div(nb, 64)), dim3(64), 0, s, sigmas_dev, sigma_scalar, nb, pc, coef);
     return ADF_LAUNCH_CHECK("edm_coef");
 }
 

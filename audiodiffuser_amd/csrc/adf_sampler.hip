@@ -34,13 +34,16 @@ int ensure_cfg_buffers(adf_handle* h, Plan* p) {
 // One denoiser evaluation.  io carries x / t / coef (preconditioning scalars already in p->coef); with classifier-free
 // guidance the network runs twice (labels, null labels) in raw mode and cfg_combine applies guidance + preconditioning.
 // Dynamic thresholding (EluDiffusion(dynamic_threshold = q), components/utils.py:23-33): the estimate leaves the combine kernel unclipped and is
-// rescaled in place by its per-sample quantile.
+// rescaled in place by its per-sample quantile.  The unclipped kind (ADF_PRECOND_V_EDM) keeps the combine fused in UNet2dBase's last kernel; on the other
+// nets, and under guidance, it is the raw pass + cfg_combine without the clamp.
 int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s) {
     const bool cfg = h->cdim > 0 && h->cond_on && h->cond_scale != 1.0f;
-    const bool dyn = h->dyn_q > 0.0f;
-    if (!cfg && !dyn) {
+    const bool noclip = h->unclipped();              // VDiffusion(for_edm=True): no clamp, and dynamic_threshold is stored but never read (diffusion.py:326)
+    const bool dyn = h->dyn_q > 0.0f && !noclip;
+    // one pass with the preconditioning in the last kernel's epilogue: clamped on every net, unclipped on UNet2dBase (u2d_conv_out_raw_kernel mode 2)
+    if (!cfg && !dyn && (!noclip || h->u2d)) {
         if (cond_rows(h, p->B, false, io)) return 1;
-        io.out = out; io.mode = 1;
+        io.out = out; io.mode = noclip ? 2 : 1;
         return forward(h, p, io, s);
     }
     const long long per_sample = (long long)h->cfg.out_channels * p->L;
@@ -58,7 +61,7 @@ int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s) {
         if (cond_rows(h, p->B, true, io) || forward(h, p, io, s)) return 1;
     }
     if (const char* e = launch_cfg_combine(out, io.x_noisy, p->cfg_c, cfg ? p->cfg_n : p->cfg_c, io.coef, io.coef_bstride, cfg ? h->cond_scale : 1.0f,
-                                           per_sample, (long long)wave, dyn ? 0 : 1, s))
+                                           per_sample, (long long)wave, (dyn || noclip) ? 0 : 1, s))
         return fail(h, e);
     if (dyn)
         if (const char* e = launch_dyn_threshold(out, p->B, per_sample, h->dyn_q, p->dyn_scale, s)) return fail(h, e);
@@ -66,7 +69,7 @@ int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s) {
 }
 
 int denoise_scalar(adf_handle* h, Plan* p, const float* x, float sigma, float sigma_data, float* out, hipStream_t s) {
-    if (const char* e = launch_edm_coef(nullptr, sigma, 1, sigma_data, p->coef, s)) return fail(h, e);
+    if (const char* e = launch_edm_coef(nullptr, sigma, 1, h->precond_for(sigma_data), p->coef, s)) return fail(h, e);
     FwdIO io;
     io.x = x; io.t = p->coef + 1; io.t_stride = 4; io.nb = 1;
     io.coef = p->coef; io.coef_bstride = 0; io.x_noisy = x;

@@ -522,6 +522,7 @@ const char* launch_u2d_attention_d128(const float* qkv, float* out, int B, int N
 
 // ------------------------------------------------------------------------------------------------ final conv, raw input
 // One thread per output pixel, all CO output channels; the weights ([co][tap][cin]) in LDS are read at one address per wave (broadcast).
+// mode 0: out = F;  mode 1: out = clamp(c_skip x_noisy + c_out F, -1, 1);  mode 2: the same without the clamp.
 template <int CO>
 __global__ void __launch_bounds__(256) u2d_conv_out_raw_kernel(const float* __restrict__ hx, const float* __restrict__ w, const float* __restrict__ bias,
                                                                float* __restrict__ out, int B, int cin, int H, int W, int mode,
@@ -561,7 +562,8 @@ __global__ void __launch_bounds__(256) u2d_conv_out_raw_kernel(const float* __re
         if (mode == 0) out[o] = F;
         else {
             const float c_skip = coef[(size_t)b * coef_bstride + 2], c_out = coef[(size_t)b * coef_bstride + 3];
-            out[o] = fminf(fmaxf(fmaf(c_out, F, c_skip * x_noisy[o]), -1.0f), 1.0f);
+            const float v = fmaf(c_out, F, c_skip * x_noisy[o]);
+            out[o] = mode == 1 ? fminf(fmaxf(v, -1.0f), 1.0f) : v;        // mode 2: the unclipped estimate (VDiffusion(for_edm=True))
         }
     }
 }

@@ -1,16 +1,19 @@
-"""``model.diffusion`` plugin: EDM preconditioning + denoise wrapper
-(reference: src/models/components/diffusion.py:15-63 ``Diffusion``, :217-257 ``EluDiffusion``).
+"""``model.diffusion`` plugins: preconditioning + denoise wrapper
+(reference: src/models/components/diffusion.py:15-63 ``Diffusion``, :99-133 ``VEDiffusion``, :136-218 ``VPDiffusion``,
+:220-258 ``EluDiffusion``, :260-365 ``VDiffusion``).
 
-``denoise_fn`` keeps the reference signature.  When ``net`` is the HIP ``UNet1dBase`` and the call
-is the inference case with clamp clipping the whole thing -- c_in scaling, sigma embedding, U-Net,
+``denoise_fn`` keeps the reference signature.  When ``net`` is one of this package's HIP nets and the call
+is the inference case the whole thing -- c_in scaling, sigma embedding, network,
 (for a class-conditional net: label embedding and classifier-free guidance), c_skip/c_out combine,
-clamp -- is one ``adf_denoise`` call.
+clipping -- is one ``adf_denoise`` call; which class's formulas the device uses travels as handle state
+(``adf_set_preconditioning``).
 For any other ``net`` (e.g. an unpickled reference module, diffunet_complex_module.py:239-242) the
 same arithmetic is expressed with tensor ops around ``net(...)``; that branch exists for interface
 compatibility and is not the accelerated path.
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional, Tuple
 
@@ -18,44 +21,52 @@ import torch
 import torch.nn as nn
 from torch import Tensor
 
-from .net import HipNet, UNet1dBase
+from . import _lib
+from .net import HipNet, UNet1dBase  # noqa: F401
 
 
 def _extend(x: Tensor, ndim: int) -> Tensor:
     return x.view(*x.shape, *((1,) * (ndim - x.ndim)))
 
 
-class EluDiffusion(nn.Module):
-    """Elucidated diffusion (EDM) preconditioning, table 1 of arXiv:2206.00364."""
+def _require_native() -> bool:
+    return os.environ.get("ADF_REQUIRE_NATIVE", "0") not in ("", "0")
 
-    def __init__(self, sigma_data: float, dynamic_threshold: float = 0.0):
+
+class Diffusion(nn.Module):
+    """What the preconditioned diffusion classes share (diffusion.py:15-97): ``denoise_fn`` with the native fast path and the
+    tensor-op compatibility branch, and the training ``forward``.  Subclasses give ``get_scale_weights`` / ``loss_weight`` and the
+    device's name for their formulas (``_precond``)."""
+
+    sigma_data = 1.0            # read by the samplers' descriptors; only EluDiffusion's formulas use it
+    _clips = True               # False: the estimate is returned as it is (VDiffusion, diffusion.py:326)
+    _mask_floor = 0.01          # weight of masked-out positions in the training loss (diffusion.py:81; VPDiffusion :209 uses 0.1)
+
+    def __init__(self, dynamic_threshold: float = 0.0):
         super().__init__()
-        self.sigma_data = sigma_data
         self.dynamic_threshold = dynamic_threshold
 
-    # diffusion.py:232-241
-    def get_scale_weights(self, sigmas: Tensor, ex_dim: int) -> Tuple[Tensor, ...]:
-        sd = self.sigma_data
-        c_noise = torch.log(sigmas) * 0.25
-        s = _extend(sigmas, ex_dim)
-        c_skip = (sd ** 2) / (s ** 2 + sd ** 2)
-        c_out = s * sd * (sd ** 2 + s ** 2) ** -0.5
-        c_in = (s ** 2 + sd ** 2) ** -0.5
-        return c_skip, c_out, c_in, c_noise
+    def _precond(self) -> Optional[tuple]:
+        """(ADF_PRECOND_* kind, beta_min, beta_d, M) of ``adf_set_preconditioning``, or None when the device has no row form for it."""
+        raise NotImplementedError
 
-    # diffusion.py:243-245
-    def loss_weight(self, sigmas: Tensor) -> Tensor:
-        return (sigmas ** 2 + self.sigma_data ** 2) * (sigmas * self.sigma_data) ** -2
+    def _not_native_note(self) -> str:
+        return ""
 
     def _native_ok(self, net, inference: bool, cond_scale: float, kwargs: dict) -> bool:
         """The HIP fast path covers inference (clamp clipping or the dynamic threshold); the only conditioning kwarg it understands is
         ``classes`` (labels) on a class-conditional net, where ``cond_scale != 1`` is classifier-free guidance."""
-        if not (isinstance(net, HipNet) and inference and 0.0 <= self.dynamic_threshold <= 1.0):
+        if not (isinstance(net, HipNet) and inference and 0.0 <= self.dynamic_threshold <= 1.0 and self._precond() is not None):
             return False
         extra = {k: v for k, v in kwargs.items() if v is not None}
         if net.cfg.class_cond:
             return set(extra) == {"classes"}
         return not extra and cond_scale == 1.0
+
+    def _configure(self, hd) -> None:
+        """Preconditioning and clipping of every evaluation the handle runs from here on."""
+        hd.set_preconditioning(*self._precond())
+        hd.set_dynamic_threshold(self.dynamic_threshold if self._clips else 0.0)
 
     # diffusion.py:32-63
     def denoise_fn(self, x_noisy: Tensor, net: nn.Module = None, inference: bool = False, cond_scale: float = 1.0,
@@ -63,7 +74,7 @@ class EluDiffusion(nn.Module):
         assert (sigma is not None) ^ (sigmas is not None), "Either x or xs must be provided"   # components/utils.py:47
         if self._native_ok(net, inference, cond_scale, kwargs) and x_noisy.is_cuda:
             hd = net.native(x_noisy.device)
-            hd.set_dynamic_threshold(self.dynamic_threshold)
+            self._configure(hd)
             x = x_noisy.detach().to(torch.float32).contiguous()
             if net.cfg.class_cond:      # labels + guidance scale for this call (diffusion.py:49-54)
                 hd.set_condition(kwargs["classes"], x.device, null_labels=False, cond_scale=float(cond_scale))
@@ -73,11 +84,16 @@ class EluDiffusion(nn.Module):
                     return hd.denoise(x, self.sigma_data, sigmas=sv).to(x_noisy.dtype)
                 return hd.denoise(x, self.sigma_data, sigma=float(sigma)).to(x_noisy.dtype)
         # ---- interface-compatibility branch: arbitrary `net` callable -------------------------
-        if isinstance(net, HipNet) and inference and os.environ.get("ADF_REQUIRE_NATIVE", "0") not in ("", "0"):
-            raise RuntimeError("denoise_fn: ADF_REQUIRE_NATIVE is set and this inference call on a HIP net would not be one adf_denoise call")
+        if isinstance(net, HipNet) and inference and _require_native():
+            raise RuntimeError("denoise_fn: ADF_REQUIRE_NATIVE is set and this inference call on a HIP net would not be one adf_denoise call"
+                               + self._not_native_note())
         b, device = x_noisy.shape[0], x_noisy.device
         if sigmas is None:
             sigmas = torch.full((b,), float(sigma), dtype=torch.float32, device=device)
+        return self._compat_denoise(x_noisy, net, inference, cond_scale, sigmas, kwargs)
+
+    def _compat_denoise(self, x_noisy: Tensor, net, inference: bool, cond_scale: float, sigmas: Tensor, kwargs: dict) -> Tensor:
+        b = x_noisy.shape[0]
         c_skip, c_out, c_in, c_noise = self.get_scale_weights(sigmas, x_noisy.ndim)
         if inference:
             pred = net(c_in * x_noisy, c_noise, cond_drop_prob=0.0, **kwargs)
@@ -94,19 +110,187 @@ class EluDiffusion(nn.Module):
         scale = _extend(scale, den.ndim)
         return den.clamp(-scale, scale) / scale
 
+    def _training_guard(self, net) -> None:
+        if isinstance(net, HipNet) and torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters()):
+            raise NotImplementedError(f"{type(self).__name__}.forward is the training loss; the HIP nets are an inference path without "
+                                      "backward -- train the reference module and load its state_dict here, or call under torch.no_grad()")
+
     # diffusion.py:65-98 (training loss; stock tensor ops, outside the accelerated path)
     def forward(self, x: Tensor, net: nn.Module, sigmas: Tensor, inference: bool = False, cond_scale: float = 1.0,
                 **kwargs) -> Tensor:
-        if isinstance(net, HipNet) and torch.is_grad_enabled() and any(p.requires_grad for p in net.parameters()):
-            raise NotImplementedError("EluDiffusion.forward is the training loss; the HIP UNet1dBase is an inference path without "
-                                      "backward -- train the reference module and load its state_dict here, or call under torch.no_grad()")
+        self._training_guard(net)
         noise = torch.randn_like(x)
         x_noisy = x + _extend(sigmas, x.ndim) * noise
         mask = torch.ones_like(x)
         if "x_mask" in kwargs:
             m = kwargs["x_mask"]
-            mask = mask * m + torch.ones_like(x) * (~m) * 0.01
+            mask = mask * m + torch.ones_like(x) * (~m) * self._mask_floor
         den = self.denoise_fn(x_noisy=x_noisy, net=net, sigmas=sigmas, inference=inference, cond_scale=cond_scale, **kwargs)
         losses = ((den - x) ** 2 * mask).reshape(x.shape[0], -1).sum(dim=1)
         per_sample = float(x[0].numel())
         return losses * self.loss_weight(sigmas) / per_sample
+
+
+class EluDiffusion(Diffusion):
+    """Elucidated diffusion (EDM) preconditioning, table 1 of arXiv:2206.00364."""
+
+    def __init__(self, sigma_data: float, dynamic_threshold: float = 0.0):
+        super().__init__(dynamic_threshold)
+        self.sigma_data = sigma_data
+
+    def _precond(self):
+        return (_lib.PRECOND_EDM, 0.0, 1.0, 1.0)
+
+    # diffusion.py:232-241
+    def get_scale_weights(self, sigmas: Tensor, ex_dim: int) -> Tuple[Tensor, ...]:
+        sd = self.sigma_data
+        c_noise = torch.log(sigmas) * 0.25
+        s = _extend(sigmas, ex_dim)
+        c_skip = (sd ** 2) / (s ** 2 + sd ** 2)
+        c_out = s * sd * (sd ** 2 + s ** 2) ** -0.5
+        c_in = (s ** 2 + sd ** 2) ** -0.5
+        return c_skip, c_out, c_in, c_noise
+
+    # diffusion.py:243-245
+    def loss_weight(self, sigmas: Tensor) -> Tensor:
+        return (sigmas ** 2 + self.sigma_data ** 2) * (sigmas * self.sigma_data) ** -2
+
+
+class VEDiffusion(Diffusion):
+    """Variance-exploding preconditioning (diffusion.py:99-133; EDM table 1, column VE)."""
+
+    def __init__(self, dynamic_threshold: float = 0.0):
+        super().__init__(dynamic_threshold)
+
+    def _precond(self):
+        return (_lib.PRECOND_VE, 0.0, 1.0, 1.0)
+
+    # diffusion.py:107-116
+    def get_scale_weights(self, sigmas: Tensor, ex_dim: int) -> Tuple:
+        c_noise = (0.5 * sigmas).log()
+        sigmas = _extend(sigmas, ex_dim)
+        return 1, sigmas, 1, c_noise
+
+    # diffusion.py:118-120
+    def loss_weight(self, sigmas: Tensor) -> Tensor:
+        return 1 / (sigmas ** 2)
+
+
+class VPDiffusion(Diffusion):
+    """Variance-preserving diffusion in EDM's formulation (diffusion.py:136-218; EDM table 1, column VP)."""
+
+    _mask_floor = 0.1           # :209
+
+    def __init__(self, beta_min: float, beta_d: float, M: float, dynamic_threshold: float = 0.0):
+        super().__init__(dynamic_threshold)
+        self.beta_min, self.beta_d, self.M = beta_min, beta_d, M
+
+    def _precond(self):
+        return (_lib.PRECOND_VP, float(self.beta_min), float(self.beta_d), float(self.M))
+
+    # diffusion.py:152-154
+    def loss_weight(self, sigmas: Tensor) -> Tensor:
+        return 1 / sigmas ** 2
+
+    # diffusion.py:156-157
+    def t_to_sigma(self, t):
+        return ((0.5 * self.beta_d * (t ** 2) + self.beta_min * t).exp() - 1).sqrt()
+
+    # diffusion.py:159-160
+    def sigma_to_t(self, sigmas):
+        return ((self.beta_min ** 2 + 2 * self.beta_d * (1 + sigmas ** 2).log()).sqrt() - self.beta_min) / self.beta_d
+
+    # diffusion.py:162-170
+    def get_scale_weights(self, sigmas: Tensor, ex_dim: int) -> Tuple:
+        c_noise = (self.M - 1) * self.sigma_to_t(sigmas)
+        sigmas = _extend(sigmas, ex_dim)
+        c_in = 1 / (sigmas ** 2 + 1).sqrt()
+        return 1, -sigmas, c_in, c_noise
+
+    # diffusion.py:185-218: `sigmas` are times t, mapped to sigma first
+    def forward(self, x: Tensor, net: nn.Module, sigmas: Tensor, inference: bool = False, cond_scale: float = 1.0, **kwargs) -> Tensor:
+        return super().forward(x, net, self.t_to_sigma(sigmas), inference=inference, cond_scale=cond_scale, **kwargs)
+
+
+class VDiffusion(Diffusion):
+    """v-prediction (diffusion.py:260-365).  ``for_edm=True`` wraps the v network as an x0 denoiser over sigma = sigma_t / alpha_t, which
+    is what the ``sampler_edm`` samplers drive: ``alpha_t x_in - sigma_t v`` with ``x_in = alpha_t x`` and ``alpha_t = sqrt(sigmoid(-2 ln sigma))``,
+    returned unclipped (``dynamic_threshold`` is stored and never read, as in the reference).  ``for_edm=False`` returns the raw v prediction
+    at the given log-SNR for the reference's ``sampler_vobj`` samplers, which this package does not build: compatibility branch only."""
+
+    _clips = False
+
+    def __init__(self, dynamic_threshold: float = 0.0, logsnr_min=-15, logsnr_max=15, shift=0.0, for_edm: bool = False):
+        super().__init__(dynamic_threshold)
+        self.logsnr_min, self.logsnr_max, self.shift, self.for_edm = logsnr_min, logsnr_max, shift, for_edm
+
+    def _precond(self):
+        return (_lib.PRECOND_V_EDM, 0.0, 1.0, 1.0) if self.for_edm else None
+
+    def _not_native_note(self) -> str:
+        return ("" if self.for_edm else ": VDiffusion(for_edm=False) feeds the reference's sampler_vobj.DPMSampler / sampler_vobj.UniPCSampler, "
+                "which are not built; only for_edm=True has a device form")
+
+    # diffusion.py:282-285
+    def shifted_cosine_transform(self, t: Tensor) -> Tensor:
+        t_min = math.atan(math.exp(-0.5 * self.logsnr_max))
+        t_max = math.atan(math.exp(-0.5 * self.logsnr_min))
+        return -2 * (torch.tan(t_min + t * (t_max - t_min)).log()) + 2 * self.shift
+
+    def sigma_to_logsnr(self, sigma):
+        return -2 * sigma.log()
+
+    def v_to_x0(self, x_noisy: Tensor, v_pred: Tensor, alphat: Tensor, sigmat: Tensor) -> Tensor:
+        return alphat * x_noisy - sigmat * v_pred
+
+    def v_to_eps(self, x_noisy: Tensor, v_pred: Tensor, alphat: Tensor, sigmat: Tensor) -> Tensor:
+        return sigmat * x_noisy + alphat * v_pred
+
+    def get_scale_weights(self, sigmas: Tensor, ex_dim: int) -> Tuple[Tensor, ...]:
+        """The ``for_edm`` wrapper (:310-313, :290) in the row form the device runs: (c_skip, c_out, c_in, c_noise) =
+        (alpha_t^2, -sigma_t, alpha_t, logsnr)."""
+        logsnr = self.sigma_to_logsnr(sigmas)
+        sigmat = _extend(torch.sqrt(torch.sigmoid(-logsnr)), ex_dim)
+        alphat = _extend(torch.sqrt(torch.sigmoid(logsnr)), ex_dim)
+        return alphat * alphat, -sigmat, alphat, logsnr
+
+    def loss_weight(self, sigmas: Tensor) -> Tensor:
+        """1 / (1 + min(snr, 5)) at the log-SNR values ``forward`` trains at (:357-358)."""
+        return 1 / (1 + torch.exp(sigmas).clamp(max=5))
+
+    # diffusion.py:306-326.  The reference multiplies x_noisy by the [B] vector alphat as it is, which broadcasts against the LAST axis and so
+    # only runs for B = 1 (or B = W); the per-sample factors are extended to [B, 1, ...] here, which gives what the reference gives sample by sample.
+    def _compat_denoise(self, x_noisy: Tensor, net, inference: bool, cond_scale: float, sigmas: Tensor, kwargs: dict) -> Tensor:
+        alphat = sigmat = None
+        if self.for_edm:
+            logsnr = self.sigma_to_logsnr(sigmas)
+            sigmat = _extend(torch.sqrt(torch.sigmoid(-logsnr)), x_noisy.ndim)
+            alphat = _extend(torch.sqrt(torch.sigmoid(logsnr)), x_noisy.ndim)
+            x_noisy = x_noisy * alphat
+            sigmas = logsnr
+        if inference:
+            v_pred = net(x_noisy, sigmas, cond_drop_prob=0.0, **kwargs)
+            if cond_scale != 1.0:
+                null = net(x_noisy, sigmas, cond_drop_prob=1.0, **kwargs)
+                v_pred = null + (v_pred - null) * cond_scale
+        else:
+            v_pred = net(x_noisy, sigmas, **kwargs)
+        return self.v_to_x0(x_noisy, v_pred, alphat, sigmat) if self.for_edm else v_pred
+
+    # diffusion.py:328-365 (training loss on the noise prediction; `sigmas` are times in [0, 1])
+    def forward(self, x: Tensor, net: nn.Module, sigmas: Tensor, inference: bool = False, cond_scale: float = 1.0, **kwargs) -> Tensor:
+        self._training_guard(net)
+        logsnr_t = self.shifted_cosine_transform(sigmas)
+        alpha_t = _extend(torch.sqrt(torch.sigmoid(logsnr_t)), x.ndim)
+        sigma_t = _extend(torch.sqrt(torch.sigmoid(-logsnr_t)), x.ndim)
+        noise = torch.randn_like(x)
+        x_noisy = alpha_t * x + sigma_t * noise
+        mask = torch.ones_like(x)
+        if "x_mask" in kwargs:
+            m = kwargs["x_mask"]
+            mask = mask * m + torch.ones_like(x) * (~m) * 0.1
+        v_pred = self.denoise_fn(x_noisy, net, sigmas=logsnr_t, inference=inference, cond_scale=cond_scale, **kwargs)
+        eps_pred = self.v_to_eps(x_noisy, v_pred, alpha_t, sigma_t)
+        weight = _extend(self.loss_weight(logsnr_t), x.ndim)
+        losses = (weight * (eps_pred - noise) ** 2 * mask).reshape(x.shape[0], -1).sum(dim=1)
+        return losses / float(x[0].numel())

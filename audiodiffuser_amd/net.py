@@ -133,6 +133,19 @@ class NativeHandle:
         """Clipping of every later denoiser evaluation: 0 = clamp(-1, 1), q = EluDiffusion(dynamic_threshold=q) (components/utils.py:19-33)."""
         self.check(self.lib.adf_set_dynamic_threshold(self.h, float(quantile)), "adf_set_dynamic_threshold")
 
+    def set_preconditioning(self, kind: int = _lib.PRECOND_EDM, beta_min: float = 0.0, beta_d: float = 1.0, M: float = 1.0) -> None:
+        """Which diffusion class's (c_in, c_noise, c_skip, c_out) every later denoiser evaluation uses (``adf_set_preconditioning``)."""
+        self.check(self.lib.adf_set_preconditioning(self.h, int(kind), float(beta_min), float(beta_d), float(M)), "adf_set_preconditioning")
+
+    def coef_rows(self, device: torch.device) -> torch.Tensor:
+        """The [n_evaluations, 4] rows (c_in, c_noise, c_skip, c_out) of the last sampler run (``adf_debug_coef_rows``)."""
+        n = C.c_int()
+        self.check(self.lib.adf_debug_coef_rows(self.h, C.c_void_p(0), 0, C.byref(n), C.c_void_p(_stream_ptr(device))), "adf_debug_coef_rows")
+        out = torch.empty((n.value, 4), device=device, dtype=torch.float32)
+        self.check(self.lib.adf_debug_coef_rows(self.h, C.c_void_p(out.data_ptr()), n.value, C.byref(n), C.c_void_p(_stream_ptr(device))),
+                   "adf_debug_coef_rows")
+        return out
+
     def denoise(self, x: torch.Tensor, sigma_data: float, sigma: Optional[float] = None,
                 sigmas: Optional[torch.Tensor] = None) -> torch.Tensor:
         out = torch.empty_like(x)

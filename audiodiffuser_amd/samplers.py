@@ -3,7 +3,7 @@
 :495-805 ``DPMSampler``).
 
 Constructor kwargs and ``forward(noise, fn, net, sigmas, **kwargs)`` follow the reference.  When ``fn``
-is ``EluDiffusion.denoise_fn`` of this package and ``net`` is the HIP ``UNet1dBase``, the whole step
+is the ``denoise_fn`` of one of this package's diffusion classes and ``net`` one of its HIP nets, the whole step
 loop runs inside ``libadf_hip.so`` (one ``adf_sampler_run`` call, optionally one hipGraph replay): all
 branch conditions of the reference loop (``gamma > 0``, ``sigma_next != 0``, warm-up orders) depend only
 on the sigma schedule, so they are resolved on the host before anything is enqueued.  For any other
@@ -20,7 +20,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import _lib
-from .diffusion import EluDiffusion
+from .diffusion import Diffusion, EluDiffusion
 from .net import HipNet, UNet1dBase
 
 
@@ -31,15 +31,18 @@ REQUIRE_NATIVE = os.environ.get("ADF_REQUIRE_NATIVE", "0") not in ("", "0")
 
 
 def _native_pair(fn: Callable, net, cond_scale: float, kwargs: dict, noise: Optional[Tensor] = None,
-                 who: str = "sampler") -> Optional[EluDiffusion]:
-    """The whole loop runs inside the HIP library when ``fn`` is this package's ``EluDiffusion.denoise_fn``, ``net`` one of
-    its HIP nets and ``noise`` lives on a ROCm device.  The only conditioning it understands is ``classes`` (labels) on a
+                 who: str = "sampler") -> Optional[Diffusion]:
+    """The whole loop runs inside the HIP library when ``fn`` is the ``denoise_fn`` of one of this package's diffusion classes
+    (``EluDiffusion``, ``VEDiffusion``, ``VPDiffusion``, ``VDiffusion(for_edm=True)``), ``net`` one of its HIP nets and ``noise``
+    lives on a ROCm device.  The only conditioning it understands is ``classes`` (labels) on a
     class-conditional net, where ``cond_scale != 1`` is classifier-free guidance (two network passes per evaluation).
     Returns the owner of ``fn`` (-> device loop) or None (-> interface-compatibility branch)."""
     owner = getattr(fn, "__self__", None)
     why = None
-    if not (isinstance(owner, EluDiffusion) and getattr(fn, "__func__", None) is EluDiffusion.denoise_fn):
-        why = "fn is not audiodiffuser_amd.EluDiffusion.denoise_fn"
+    if not (isinstance(owner, Diffusion) and getattr(fn, "__func__", None) is Diffusion.denoise_fn):
+        why = "fn is not the denoise_fn of one of audiodiffuser_amd's diffusion classes"
+    elif owner._precond() is None:
+        why = "this diffusion class has no device form" + owner._not_native_note()
     elif not isinstance(net, HipNet):
         why = "net is not one of this package's HIP networks"
     elif not 0.0 <= owner.dynamic_threshold <= 1.0:
@@ -60,10 +63,15 @@ def _native_pair(fn: Callable, net, cond_scale: float, kwargs: dict, noise: Opti
     return None
 
 
-def _condition(net: UNet1dBase, hd, device, cond_scale: float, kwargs: dict, diff: Optional[EluDiffusion] = None) -> None:
+def _condition(net: UNet1dBase, hd, device, cond_scale: float, kwargs: dict, diff: Optional[Diffusion] = None) -> None:
     """Labels + guidance scale of this sampler run (the reference forwards them to every fn call, e.g.
-    sampler_edm.py:341-345), and the clipping of the owner of ``fn`` (clamp or dynamic threshold, diffusion.py:61)."""
-    hd.set_dynamic_threshold(diff.dynamic_threshold if diff is not None else 0.0)
+    sampler_edm.py:341-345), and the preconditioning and clipping of the owner of ``fn`` (its get_scale_weights; clamp, dynamic
+    threshold or -- VDiffusion -- none, diffusion.py:61, :326)."""
+    if diff is not None:
+        diff._configure(hd)
+    else:
+        hd.set_preconditioning()
+        hd.set_dynamic_threshold(0.0)
     if net.cfg.class_cond:
         hd.set_condition(kwargs["classes"], device, null_labels=False, cond_scale=float(cond_scale))
 

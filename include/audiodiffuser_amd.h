@@ -48,8 +48,11 @@ extern "C" {
  * 4: ADF_FLAG_NEAREST_UPSAMPLE (adf_net_config.flags bit 1; state-dict keys ...upsample.2.weight / .bias), WaveNetNoise in bf16 at 64 / 128
  *    residual channels, adf_debug_tap on a WaveNet handle keeps every layer while all of them fit 512 MiB (256 MiB before).
  * 5: ADF_DTYPE_F32X3 (a third value of adf_net_config.dtype: fp32 storage, every GEMM operand split into bf16 hi + lo, three bf16 MFMAs per product).
- * 6: adf_unet2d_config / adf_unet2d_create (the Imagen-style UNet2dBase, exact fp32). */
-#define ADF_ABI_VERSION 6
+ * 6: adf_unet2d_config / adf_unet2d_create (the Imagen-style UNet2dBase, exact fp32).
+ * 7: adf_set_preconditioning (ADF_PRECOND_EDM / VE / VP / V_EDM) and adf_debug_coef_rows.  The preconditioning kind travels as handle state, in the
+ *    style of adf_set_dynamic_threshold: adf_sampler_desc and the argument list of adf_denoise are unchanged, so a caller that fills only the
+ *    fields of version 6 and never calls the setter still gets EluDiffusion's rows. */
+#define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
 #define ADF_MAX_LAYERS 12
@@ -163,6 +166,23 @@ int adf_set_image_shape(adf_handle* h, int H, int W);
  * thresholding of EluDiffusion(dynamic_threshold = q) -- per sample, scale = max(1, quantile(|x|, q)) (torch.quantile's linear interpolation),
  * x = clamp(x, -scale, scale) / scale.  Replaces src/models/components/utils.py:19-33 (`clip`) as called from diffusion.py:61. */
 int adf_set_dynamic_threshold(adf_handle* h, float quantile);
+
+/* Preconditioning of every denoiser evaluation from here on (adf_denoise, adf_sampler_run): which formulas turn a sigma into the row
+ * (c_in, c_noise, c_skip, c_out) of out = clip(c_skip * x + c_out * net(c_in * x, c_noise)).  All in fp32 in the reference's order of operations
+ * (src/models/components/diffusion.py):
+ *   ADF_PRECOND_EDM    EluDiffusion  :232-241  ((s^2 + sd^2)^-1/2, ln(s) / 4, sd^2 / (s^2 + sd^2), s sd (s^2 + sd^2)^-1/2); sd = the sigma_data argument of
+ *                                              adf_denoise / adf_sampler_desc (the default of a new handle)
+ *   ADF_PRECOND_VE     VEDiffusion   :107-116  (1, ln(s / 2), 1, s)
+ *   ADF_PRECOND_VP     VPDiffusion   :156-170  ((s^2 + 1)^-1/2, (M - 1) t(s), 1, -s), t(s) = (sqrt(beta_min^2 + 2 beta_d ln(1 + s^2)) - beta_min) / beta_d
+ *   ADF_PRECOND_V_EDM  VDiffusion(for_edm=True) :296-326  (a, -2 ln s, a^2, -sqrt(sigmoid(2 ln s))), a = sqrt(sigmoid(-2 ln s)).  The estimate is returned
+ *                                              UNCLIPPED, as in the reference: neither the clamp nor the dynamic threshold applies.
+ * beta_min, beta_d, M are read for ADF_PRECOND_VP only (doubles: beta_min^2, 2 beta_d and M - 1 are formed in double and then rounded to fp32, as torch
+ * rounds the reference's Python scalars); sigma_data is ignored by every kind but ADF_PRECOND_EDM. */
+#define ADF_PRECOND_EDM 0
+#define ADF_PRECOND_VE 1
+#define ADF_PRECOND_VP 2
+#define ADF_PRECOND_V_EDM 3
+int adf_set_preconditioning(adf_handle* h, int kind, double beta_min, double beta_d, double M);
 /* A WaveNetNoise handle.  x / out of adf_net_forward, adf_denoise, adf_sampler_run are [B][1][T] (the reference's forward takes
  * audio [B][T] and returns [B][1][T]: same memory); any T >= 1.  Debug taps: "y<n>" = input of residual layer n including its
  * diffusion-step addend (kept while all of them fit 512 MiB), "skip" = the normalised skip sum. */
@@ -188,7 +208,8 @@ int adf_set_condition(adf_handle* h, const int64_t* classes_dev, int B, int null
 /* out = net(x, t):  x [B][in_channels][L], t [B], out [B][out_channels][L] */
 int adf_net_forward(adf_handle* h, const float* x, const float* t, float* out, int B, int L, void* stream);
 
-/* out = clamp(c_skip*x + c_out*net(c_in*x, c_noise), -1, 1); sigmas_dev [B] or NULL (then `sigma` for all) */
+/* out = clamp(c_skip*x + c_out*net(c_in*x, c_noise), -1, 1); sigmas_dev [B] or NULL (then `sigma` for all).  The rows and the clipping are those of
+ * adf_set_preconditioning / adf_set_dynamic_threshold (defaults: EluDiffusion with `sigma_data`, clamp). */
 int adf_denoise(adf_handle* h, const float* x_noisy, const float* sigmas_dev, float sigma, float sigma_data,
                 float* out, int B, int L, void* stream);
 
@@ -207,6 +228,9 @@ int adf_debug_tap_shape(adf_handle* h, const char* name, int* C, int* L);
 int adf_debug_tap_copy(adf_handle* h, const char* name, float* out_fp32, void* stream);
 /* The dynamic threshold alone, in place on x_dev [B][per_sample] (tests: exactness of the order statistics against torch.quantile). */
 int adf_debug_dyn_threshold(adf_handle* h, float* x_dev, int B, long long per_sample, float quantile, void* stream);
+/* The (c_in, c_noise, c_skip, c_out) rows of the last adf_sampler_run on this handle, one per denoiser evaluation in order: copies
+ * min(max_rows, rows) * 4 floats to out_dev (device) and returns the number of rows of that run through *n_rows. */
+int adf_debug_coef_rows(adf_handle* h, float* out_dev, int max_rows, int* n_rows, void* stream);
 int adf_debug_tap_count(adf_handle* h);
 const char* adf_debug_tap_name(adf_handle* h, int index);
 
