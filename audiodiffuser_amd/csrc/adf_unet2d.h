@@ -48,7 +48,8 @@ const char* launch_u2d_gate_residual(const float* h, const float* gate, const fl
 // PixelShuffleUpsample (:27-55) after its 1x1 conv: out[b][(2y + s1) * 2W + 2x + s2][c] = SiLU(in[b][y * W + x][4 c + 2 s1 + s2])
 const char* launch_u2d_silu_shuffle(const float* in, float* out, int B, int H, int W, int C, hipStream_t s);
 
-// FeedForward (attention_utils.py:186-194) middle: y = LayerNorm_g(GELU(x)) over the last dim (exact erf GELU, biased variance, gain only)
+// FeedForward (attention_utils.py:186-194) middle: y = LayerNorm_g(GELU(x)) over the last dim (exact erf GELU, biased variance, gain only).
+// C a multiple of 4, at most 1024: the widest row the net can hand it (the Linear behind it reads at most 1024 input channels).
 const char* launch_u2d_gelu_ln_rows(const float* x, float* y, long long rows, int C, const float* g, float eps, hipStream_t s);
 
 // Self-attention at head dim 128 (attention_utils.py:160-182) in exact fp32 on a fused [B][N][3C] q | k | v tensor -> out [B][N][C].

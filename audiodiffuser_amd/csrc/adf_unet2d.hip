@@ -387,7 +387,7 @@ const char* launch_u2d_silu_shuffle(const float* in, float* out, int B, int H, i
 }
 
 // ------------------------------------------------------------------------------------------------ LayerNorm_g(GELU(x))
-// One wave per row, CPL 16-byte pieces per lane (C <= 256 CPL); two passes over the register copy (mean, then centred squares)
+// One wave per row, CPL 16-byte pieces per lane (C <= 256 CPL, CPL 1, 2 or 4); two passes over the register copy (mean, then centred squares)
 template <int CPL>
 __global__ void __launch_bounds__(256) u2d_gelu_ln_kernel(const float* __restrict__ x, float* __restrict__ y, long long rows, int C,
                                                           const float* __restrict__ g, float eps) {
@@ -433,8 +433,7 @@ const char* launch_u2d_gelu_ln_rows(const float* x, float* y, long long rows, in
     if (cpr <= 64) hipLaunchKernelGGL(u2d_gelu_ln_kernel<1>, dim3(grid), dim3(256), 0, s, x, y, rows, C, g, eps);
     else if (cpr <= 128) hipLaunchKernelGGL(u2d_gelu_ln_kernel<2>, dim3(grid), dim3(256), 0, s, x, y, rows, C, g, eps);
     else if (cpr <= 256) hipLaunchKernelGGL(u2d_gelu_ln_kernel<4>, dim3(grid), dim3(256), 0, s, x, y, rows, C, g, eps);
-    else if (cpr <= 512) hipLaunchKernelGGL(u2d_gelu_ln_kernel<8>, dim3(grid), dim3(256), 0, s, x, y, rows, C, g, eps);
-    else return "u2d_gelu_ln_rows: C above 2048";
+    else return "u2d_gelu_ln_rows: C above 1024";
     return U2D_LAUNCH_CHECK("u2d_gelu_ln_rows");
 }
 

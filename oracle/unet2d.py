@@ -324,19 +324,28 @@ def global_context(p: P, pre: str, x: torch.Tensor) -> torch.Tensor:
     return torch.sigmoid(conv2d(p, f"{pre}.net.2", h))
 
 
-def resnet_block(p: P, pre: str, x: torch.Tensor, t: Optional[torch.Tensor], groups: int) -> torch.Tensor:
+def resnet_block(p: P, pre: str, x: torch.Tensor, t: Optional[torch.Tensor], groups: int, fine=None, name: str = "") -> torch.Tensor:
     """ResnetBlock.forward :147-168 with ``cond=None`` (the cross-attention branch :157-162 is never taken by UNet2dBase.forward, which
     passes ``c=None`` everywhere :928-946): time_mlp -> (scale, shift) for block2 only; gca gate (or the constant 1); 1x1 residual conv
-    when the widths differ."""
+    when the widths differ.  ``fine(key, tensor)``: records ``name.h1`` (block1), ``name.res`` (the 1x1 residual conv, when there is one),
+    ``name.h2`` (block2 before the gate, when there is a gate) and ``name`` (the block's output)."""
+    fine = fine or (lambda k, v: None)
     scale_shift = None
     if t is not None and f"{pre}.time_mlp.1.weight" in p:
         te = F.linear(F.silu(t), p[f"{pre}.time_mlp.1.weight"], p[f"{pre}.time_mlp.1.bias"])[:, :, None, None]
         scale_shift = te.chunk(2, dim=1)
     h = block(p, f"{pre}.block1", x, groups)
+    fine(f"{name}.h1", h)
     h = block(p, f"{pre}.block2", h, groups, scale_shift)
     if f"{pre}.gca.to_k.weight" in p:
+        fine(f"{name}.h2", h)
         h = h * global_context(p, f"{pre}.gca", h)
-    res = conv2d(p, f"{pre}.res_conv", x) if f"{pre}.res_conv.weight" in p else x
+    if f"{pre}.res_conv.weight" in p:
+        res = conv2d(p, f"{pre}.res_conv", x)
+        fine(f"{name}.res", res)
+    else:
+        res = x
+    fine(name, h + res)
     return h + res
 
 
@@ -347,16 +356,24 @@ def layer_norm_g(x: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     return (x - mean) * (var + 1e-5).rsqrt() * g
 
 
-def attention(p: P, pre: str, x: torch.Tensor, heads: int) -> torch.Tensor:
-    """attention_utils.py:113-184, the branch without context (:157-158: no rotary embedding there), no mask, no qk l2norm.  x: [B, N, C]."""
+def attention(p: P, pre: str, x: torch.Tensor, heads: int, fine=None, name: str = "") -> torch.Tensor:
+    """attention_utils.py:113-184, the branch without context (:157-158: no rotary embedding there), no mask, no qk l2norm.  x: [B, N, C].
+    The softmax runs in fp32 as in the reference, or in float64 when x is float64 (the double-precision run the device is held to).
+    ``fine``: records ``name.qkv`` (q | k | v along channels) and ``name.att`` (the heads merged back, before ``to_out``), both [B, N, C']."""
     b, n, c = x.shape
     d = c // heads
     q = F.linear(x, p[f"{pre}.to_q.weight"])
-    k, v = F.linear(x, p[f"{pre}.to_kv.weight"]).chunk(2, dim=-1)
+    kv = F.linear(x, p[f"{pre}.to_kv.weight"])
+    if fine is not None:
+        fine(f"{name}.qkv", torch.cat((q, kv), dim=-1))
+    k, v = kv.chunk(2, dim=-1)
     q, k, v = (z.reshape(b, n, heads, d).permute(0, 2, 1, 3) for z in (q, k, v))
     sim = torch.matmul(q, k.transpose(-1, -2)) * (d ** -0.5)
-    out = torch.matmul(sim.softmax(dim=-1, dtype=torch.float32), v)
-    return F.linear(out.permute(0, 2, 1, 3).reshape(b, n, c), p[f"{pre}.to_out.weight"])
+    out = torch.matmul(sim.softmax(dim=-1, dtype=torch.float64 if x.dtype == torch.float64 else torch.float32), v)
+    out = out.permute(0, 2, 1, 3).reshape(b, n, c)
+    if fine is not None:
+        fine(f"{name}.att", out)
+    return F.linear(out, p[f"{pre}.to_out.weight"])
 
 
 def feed_forward(p: P, pre: str, x: torch.Tensor) -> torch.Tensor:
@@ -365,15 +382,24 @@ def feed_forward(p: P, pre: str, x: torch.Tensor) -> torch.Tensor:
     return F.linear(layer_norm_g(F.gelu(h), p[f"{pre}.3.g"]), p[f"{pre}.4.weight"])
 
 
-def transformer_block(p: P, pre: str, x: torch.Tensor, heads: int) -> torch.Tensor:
-    """TransformerBlock.forward :219-232 without context: tokens = pixels; per layer x = attn(norm(x)) + x (ONE shared norm), x = ff(x) + x."""
+def transformer_block(p: P, pre: str, x: torch.Tensor, heads: int, fine=None, name: str = "") -> torch.Tensor:
+    """TransformerBlock.forward :219-232 without context: tokens = pixels; per layer x = attn(norm(x)) + x (ONE shared norm), x = ff(x) + x.
+    ``fine``: per layer ``name.layers.d.qkv`` / ``.att`` (see ``attention``), ``.x1`` (after the attention residual) and ``name.layers.d``
+    (the layer's output), then ``name`` (the block's output); token tensors [B, N, C]."""
     b, c, hh, ww = x.shape
     tok = x.permute(0, 2, 3, 1).reshape(b, hh * ww, c)
     d = 0
     while f"{pre}.layers.{d}.0.to_q.weight" in p:
-        tok = attention(p, f"{pre}.layers.{d}.0", layer_norm_g(tok, p[f"{pre}.norm.g"]), heads) + tok
+        ln = f"{name}.layers.{d}"
+        tok = attention(p, f"{pre}.layers.{d}.0", layer_norm_g(tok, p[f"{pre}.norm.g"]), heads, fine, ln) + tok
+        if fine is not None:
+            fine(f"{ln}.x1", tok)
         tok = feed_forward(p, f"{pre}.layers.{d}.1", tok) + tok
+        if fine is not None:
+            fine(ln, tok)
         d += 1
+    if fine is not None:
+        fine(name, tok)
     return tok.reshape(b, hh, ww, c).permute(0, 3, 1, 2)
 
 
@@ -382,22 +408,34 @@ def downsample(p: P, pre: str, x: torch.Tensor) -> torch.Tensor:
     return conv2d(p, f"{pre}.1", F.pixel_unshuffle(x, 2))
 
 
-def upsample(p: P, pre: str, x: torch.Tensor, pixel_shuffle: bool) -> torch.Tensor:
-    """PixelShuffleUpsample.forward :54-55 (1x1 conv to 4x the channels, SiLU, PixelShuffle(2)) or Upsample :19-25 (nearest x2, 3x3 conv)."""
+def upsample(p: P, pre: str, x: torch.Tensor, pixel_shuffle: bool, fine=None, name: str = "") -> torch.Tensor:
+    """PixelShuffleUpsample.forward :54-55 (1x1 conv to 4x the channels, SiLU, PixelShuffle(2)) or Upsample :19-25 (nearest x2, 3x3 conv).
+    ``fine``: records ``name.conv``, the 1x1 conv's output before SiLU and shuffle."""
     if pixel_shuffle:
-        return F.pixel_shuffle(F.silu(conv2d(p, f"{pre}.net.0", x)), 2)
+        h = conv2d(p, f"{pre}.net.0", x)
+        if fine is not None:
+            fine(f"{name}.conv", h)
+        return F.pixel_shuffle(F.silu(h), 2)
     return conv2d(p, f"{pre}.1", F.interpolate(x, scale_factor=2, mode="nearest"), padding=1)
 
 
 # ------------------------------------------------------------------ the network
 def unet2d_forward(p: P, cfg: UNet2dConfig, x: torch.Tensor, time: torch.Tensor, classes: Optional[torch.Tensor] = None,
-                   cond_drop_prob: float = 0.0, taps: Optional[dict] = None) -> torch.Tensor:
+                   cond_drop_prob: float = 0.0, taps: Optional[dict] = None, fine_taps: Optional[dict] = None) -> torch.Tensor:
     """UNet2dBase.forward :879-970 for ``text_embeds=None`` and ``inj_channels=None``.  x: [B, channels, H, W] with H and W multiples of
     2^levels; time: [B] (the EDM wrapper passes c_noise); classes: int64 [B] when ``num_classes != 0``.
     ``taps``: receives the output of every module whose output the generator hooks in the reference ("init_conv", "init_resnet_block",
-    "downs.i", "mid_block", "ups.i", "final_res_block")."""
+    "downs.i", "mid_block", "ups.i", "final_res_block").
+    ``fine_taps`` (opt-in): receives a tensor under every name the device walker records (``walker_tap_names``), flattened to the
+    device's tap layout [B, C, H * W]: the pieces of every resnet block and transformer layer, ``downs.i.down``, ``ups.i.3.conv``, and the
+    block-level outputs above."""
     cfg.check()
     rec = (lambda k, v: taps.__setitem__(k, v)) if taps is not None else (lambda k, v: None)
+
+    def fine(k, v):                                          # images [B, C, H, W] and token rows [B, N, C] -> [B, C, H * W]
+        fine_taps[k] = v.flatten(2) if v.ndim == 4 else v.transpose(1, 2)
+    if fine_taps is None:
+        fine = None
     g = cfg.resnet_groups
     heads = cfg.attn_heads
     n = len(cfg.in_out)
@@ -408,6 +446,8 @@ def unet2d_forward(p: P, cfg: UNet2dConfig, x: torch.Tensor, time: torch.Tensor,
     else:
         x = conv2d(p, "init_conv", x, padding=cfg.init_conv_kernel_size // 2)
     rec("init_conv", x)
+    if fine:
+        fine("init_conv", x)
     # :898-908 conditioning vector
     t = time_conditioning(p, time)
     if cfg.num_classes != 0:
@@ -415,7 +455,7 @@ def unet2d_forward(p: P, cfg: UNet2dConfig, x: torch.Tensor, time: torch.Tensor,
         t = t + label_embedding(p, classes, cond_drop_prob)
     # :918-921
     if cfg.memory_efficient:
-        x = resnet_block(p, "init_resnet_block", x, t, g)
+        x = resnet_block(p, "init_resnet_block", x, t, g, fine, "init_resnet_block")
         rec("init_resnet_block", x)
     # :924-946 down path (DownsamplingBlock.forward :404-436)
     hiddens: List[torch.Tensor] = []
@@ -423,12 +463,14 @@ def unet2d_forward(p: P, cfg: UNet2dConfig, x: torch.Tensor, time: torch.Tensor,
         pre = f"downs.{i}.ds_block"
         if cfg.memory_efficient:
             x = downsample(p, f"{pre}.0", x)
-        x = resnet_block(p, f"{pre}.1", x, t, g)
+            if fine:
+                fine(f"downs.{i}.down", x)
+        x = resnet_block(p, f"{pre}.1", x, t, g, fine, f"downs.{i}.1")
         for j in range(cfg.num_resnet_blocks):
-            x = resnet_block(p, f"{pre}.2.{j}", x, t, g)
+            x = resnet_block(p, f"{pre}.2.{j}", x, t, g, fine, f"downs.{i}.2.{j}")
             hiddens.append(x)
         if cfg.layer_attns[i]:
-            x = transformer_block(p, f"{pre}.3", x, heads)
+            x = transformer_block(p, f"{pre}.3", x, heads, fine, f"downs.{i}.3")
         hiddens.append(x)
         if not cfg.memory_efficient:
             if i < n - 1:
@@ -436,28 +478,79 @@ def unet2d_forward(p: P, cfg: UNet2dConfig, x: torch.Tensor, time: torch.Tensor,
             else:
                 x = conv2d(p, f"{pre}.4.fns.0", x, padding=1) + conv2d(p, f"{pre}.4.fns.1", x)
         rec(f"downs.{i}", x)
+        if fine:
+            fine(f"downs.{i}", x)
     # :948 (MiddleBlock.forward :461-469)
-    x = resnet_block(p, "mid_block.mid_block1", x, t, g)
+    x = resnet_block(p, "mid_block.mid_block1", x, t, g, fine, "mid_block.mid_block1")
     if cfg.attend_at_middle:
-        x = transformer_block(p, "mid_block.mid_attn", x, heads)
-    x = resnet_block(p, "mid_block.mid_block2", x, t, g)
+        x = transformer_block(p, "mid_block.mid_attn", x, heads, fine, "mid_block.mid_attn")
+    x = resnet_block(p, "mid_block.mid_block2", x, t, g, fine, "mid_block.mid_block2")
     rec("mid_block", x)
+    if fine:
+        fine("mid_block", x)
     # :950-958 up path (UpsamplingBlock.forward :524-538)
     s = cfg.skip_scale
     for i in range(n):
         li = n - 1 - i
         pre = f"ups.{i}.us_block"
-        x = resnet_block(p, f"{pre}.0", torch.cat((x, hiddens.pop() * s), dim=1), t, g)
+        x = resnet_block(p, f"{pre}.0", torch.cat((x, hiddens.pop() * s), dim=1), t, g, fine, f"ups.{i}.0")
         for j in range(cfg.num_resnet_blocks):
-            x = resnet_block(p, f"{pre}.1.{j}", torch.cat((x, hiddens.pop() * s), dim=1), t, g)
+            x = resnet_block(p, f"{pre}.1.{j}", torch.cat((x, hiddens.pop() * s), dim=1), t, g, fine, f"ups.{i}.1.{j}")
         if cfg.layer_attns[li]:
-            x = transformer_block(p, f"{pre}.2", x, heads)
+            x = transformer_block(p, f"{pre}.2", x, heads, fine, f"ups.{i}.2")
         if i < n - 1 or cfg.memory_efficient:
-            x = upsample(p, f"{pre}.3", x, cfg.pixel_shuffle_upsample)
+            x = upsample(p, f"{pre}.3", x, cfg.pixel_shuffle_upsample, fine, f"ups.{i}.3")
         rec(f"ups.{i}", x)
+        if fine:
+            fine(f"ups.{i}", x)
     assert not hiddens                                                     # :960
     # :969-972
     if cfg.final_resnet_block:
-        x = resnet_block(p, "final_res_block", x, t, g)
+        x = resnet_block(p, "final_res_block", x, t, g, fine, "final_res_block")
         rec("final_res_block", x)
     return conv2d(p, "final_conv", x, padding=cfg.final_conv_kernel_size // 2)
+
+
+def walker_tap_names(cfg: UNet2dConfig) -> List[str]:
+    """The names the device walker records for this structure (memory-efficient, global-context, pixel-shuffle layout), in walk order:
+    what ``fine_taps`` must hold a tensor for."""
+    out: List[str] = ["init_conv"]
+
+    def rb(name: str, res: bool, gca: bool) -> None:
+        out.append(f"{name}.h1")
+        if res:
+            out.append(f"{name}.res")
+        if gca:
+            out.append(f"{name}.h2")
+        out.append(name)
+
+    def tr(name: str, depth: int) -> None:
+        for d in range(depth):
+            out.extend(f"{name}.layers.{d}{s}" for s in (".qkv", ".att", ".x1", ""))
+        out.append(name)
+
+    n = len(cfg.dim_mults)
+    rb("init_resnet_block", False, True)
+    for i in range(n):
+        out.append(f"downs.{i}.down")
+        rb(f"downs.{i}.1", False, False)
+        for j in range(cfg.num_resnet_blocks):
+            rb(f"downs.{i}.2.{j}", False, True)
+        if cfg.layer_attns[i]:
+            tr(f"downs.{i}.3", cfg.layer_attns_depth)
+        out.append(f"downs.{i}")
+    rb("mid_block.mid_block1", False, False)
+    if cfg.attend_at_middle:
+        tr("mid_block.mid_attn", cfg.layer_mid_attns_depth)
+    rb("mid_block.mid_block2", False, False)
+    out.append("mid_block")
+    for i in range(n):
+        rb(f"ups.{i}.0", True, False)
+        for j in range(cfg.num_resnet_blocks):
+            rb(f"ups.{i}.1.{j}", True, True)
+        if cfg.layer_attns[n - 1 - i]:
+            tr(f"ups.{i}.2", cfg.layer_attns_depth)
+        out.extend((f"ups.{i}.3.conv", f"ups.{i}"))
+    if cfg.final_resnet_block:
+        rb("final_res_block", False, True)
+    return out
