@@ -1,10 +1,8 @@
 // C-ABI implementation (include/audiodiffuser_amd.h): weight registry keyed by the reference state_dict
-// names, per-(B, L) workspace, the U-Net walk that launches the fused kernels, and the sampler drivers
-// (EDM Heun/churn, EDM-alpha, DPM-Solver multistep) with whole-loop hipGraph capture.
+// names, per-(B, L) workspace, and the sampler entry point (EDM Heun/churn, EDM-alpha, DPM-Solver multistep, ...) with
+// whole-loop hipGraph capture.  The network a handle drives is its Net (adf_api_internal.h; one per adf_net_*.hip).
 //
 // Host logic mirrors (does not copy) the reference control flow:
-//   UNet1d.forward            src/models/backbones/unet1d.py:771-816
-//   Down/UpsampleBlock1d      src/models/backbones/unet1d.py:441-468, :542-566
 //   Diffusion.denoise_fn      src/models/components/diffusion.py:32-63
 //   EDMSampler / Alpha / DPM  src/models/components/sampler_edm.py:333-397, :251-300, :624-768
 #include "adf_api_internal.h"
@@ -17,27 +15,11 @@ namespace adf_api {
 std::string g_create_error;
 
 int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out) {
-    const adf_net_config& c = h->cfg;
-    int total = c.stride;
-    for (int i = 0; i < c.num_layers; ++i) total *= c.factors[i];
-    if (B < 1 || L < 1 || L % total) return fail(h, "length must be a positive multiple of the total down-sampling factor");
+    const NetDims& c = h->net->dims;
+    if (B < 1 || L < 1 || L % c.length_multiple) return fail(h, "length must be a positive multiple of the total down-sampling factor");
     if (adf_weights_missing(h)) return fail(h, "weights are not fully loaded");
-    if (h->wn && !h->wn->packed && wn_pack_weights(h, s)) return 1;
-    if (h->adm) {
-        const AdmW& a = *h->adm;
-        int f = 1;
-        for (int i = 1; i < a.cfg.n_mult; ++i) f *= 2;
-        if (a.H < 1 || a.W < 1 || (long long)a.H * a.W != L) return fail(h, "UNetModel: call adf_set_image_shape(H, W) with H * W equal to the length argument first");
-        if (a.H % f || a.W % f || ((a.H / f) * (a.W / f)) % 64)
-            return fail(h, "UNetModel: H and W must be multiples of 2^(levels-1) and the coarsest level a multiple of 64 pixels");
-    }
-    if (h->u2d) {
-        const U2dW& u = *h->u2d;
-        const int f = 1 << u.cfg.n_levels;
-        if (u.H < 1 || u.W < 1 || (long long)u.H * u.W != L) return fail(h, "UNet2dBase: call adf_set_image_shape(H, W) with H * W equal to the length argument first");
-        if (u.H % f || u.W % f) return fail(h, "UNet2dBase: H and W must be multiples of 2^levels");
-    }
-    const std::tuple<int, int, int> pkey{B, L, h->adm ? h->adm->H : (h->u2d ? h->u2d->H : 0)};
+    if (h->net->prepare(h, s) || h->net->check_image(h, L)) return 1;
+    const std::tuple<int, int, int> pkey{B, L, h->net->image ? h->net->H : 0};
     auto it = h->plans.find(pkey);
     if (it != h->plans.end()) { *out = it->second; h->last_plan = it->second; it->second->last_use = ++h->use_clock; return 0; }
     Plan* p = new Plan();
@@ -60,7 +42,7 @@ int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out) {
     p->arena = (char*)dalloc(h, p->arena_bytes, p);
     p->stats = (char*)dalloc(h, p->stats_bytes ? p->stats_bytes : 256, p);
     const size_t wave = (size_t)B * c.out_channels * L;
-    p->temb = (float*)dalloc(h, (size_t)B * 4 * c.channels * 4, p);
+    p->temb = (float*)dalloc(h, (size_t)B * c.temb * 4, p);
     p->film = (float*)dalloc(h, (size_t)B * h->film_total * 4, p);
     p->coef = (float*)dalloc(h, (size_t)B * 4 * 4, p);
     bool ok = p->arena && p->stats && p->temb && p->film && p->coef;
@@ -84,144 +66,43 @@ int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out) {
     return 0;
 }
 
+int forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
+    if (!p->dry) ++h->ctr.net_passes;
+    return h->net->forward(h, p, io, s);
+}
+
+int create_begin(const char* fn, const void* cfg, adf_handle** out) {
+    if (!cfg || !out) { g_create_error = std::string(fn) + ": null argument"; return 1; }
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = std::string(fn) + ": no HIP device available"; return 1; }
+    return 0;
+}
+
+int create_finish(const char* fn, int dtype, std::unique_ptr<Net> net, adf_handle** out) {
+    adf_handle* h = new adf_handle();
+    if (hipGetDevice(&h->device) != hipSuccess) { g_create_error = std::string(fn) + ": hipGetDevice failed"; delete h; return 1; }
+    h->bf16 = dtype == ADF_DTYPE_BF16;
+    h->x3 = dtype == ADF_DTYPE_F32X3;               // fp32 storage (esz 4, 32 K elements per row) with split-bf16 GEMM operands
+    h->esz = h->bf16 ? 2 : 4;
+    h->kc = kRowBytes / h->esz;
+    h->net = std::move(net);
+    if (h->net->build_weights(h)) { g_create_error = h->err; adf_destroy(h); return 1; }
+    *out = h;
+    return 0;
+}
+
 }  // namespace adf_api
 
 // =====================================================================================================
-// C ABI
+// C ABI (adf_create, adf_wavenet_create, adf_adm_create, adf_unet2d_create: beside their networks, adf_net_*.hip)
 // =====================================================================================================
 extern "C" {
 
-int adf_create(const adf_net_config* cfg, adf_handle** out) {
-    if (!cfg || !out) { g_create_error = "adf_create: null argument"; return 1; }
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "adf_create: no HIP device available"; return 1; }
-    const adf_net_config& c = *cfg;
-    if (c.num_layers < 1 || c.num_layers > ADF_MAX_LAYERS) { g_create_error = "adf_create: bad num_layers"; return 1; }
-    if (c.num_filters != c.channels * c.multipliers[0]) { g_create_error = "adf_create: num_filters must equal channels*multipliers[0]"; return 1; }
-    if (c.channels % 2 || c.channels < 2) { g_create_error = "adf_create: channels must be even"; return 1; }
-    if (c.dtype != ADF_DTYPE_F32 && c.dtype != ADF_DTYPE_BF16 && c.dtype != ADF_DTYPE_F32X3) { g_create_error = "adf_create: bad dtype"; return 1; }
-    adf_handle* h = new adf_handle();
-    h->cfg = c;
-    if (hipGetDevice(&h->device) != hipSuccess) { g_create_error = "adf_create: hipGetDevice failed"; delete h; return 1; }
-    h->bf16 = c.dtype == ADF_DTYPE_BF16;
-    h->x3 = c.dtype == ADF_DTYPE_F32X3;             // fp32 storage (esz 4, 32 K elements per row) with split-bf16 GEMM operands
-    h->esz = h->bf16 ? 2 : 4;
-    h->kc = kRowBytes / h->esz;
-    if (build_weights(h)) { g_create_error = h->err; adf_destroy(h); return 1; }
-    *out = h;
-    return 0;
-}
-
-int adf_wavenet_create(const adf_wavenet_config* cfg, adf_handle** out) {
-    if (!cfg || !out) { g_create_error = "adf_wavenet_create: null argument"; return 1; }
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "adf_wavenet_create: no HIP device available"; return 1; }
-    const adf_wavenet_config& c = *cfg;
-    if (c.residual_channels < 32 || c.residual_channels % 32 || c.residual_channels > 512) { g_create_error = "adf_wavenet_create: residual_channels must be a multiple of 32 in [32, 512]"; return 1; }
-    if (c.residual_layers < 1 || c.residual_layers > 1024 || c.dilation_cycle < 1 || c.dilation_cycle > 24) { g_create_error = "adf_wavenet_create: bad residual_layers / dilation_cycle"; return 1; }
-    if (c.dim_in < 4 || c.dim_in % 2 || c.dim_in > 1024 || c.dim_mid < 1 || c.dim_mid > 1024 || c.dim_out < 4 || c.dim_out % 4 || c.dim_out > 1024) { g_create_error = "adf_wavenet_create: bad embedding widths"; return 1; }
-    if (c.dtype != ADF_DTYPE_F32 && c.dtype != ADF_DTYPE_BF16) { g_create_error = "adf_wavenet_create: bad dtype"; return 1; }
-    if (c.dtype == ADF_DTYPE_BF16 && c.residual_channels != 256 && c.residual_channels != 128 && c.residual_channels != 64) { g_create_error = "adf_wavenet_create: the bf16 (MFMA) kernels are built for residual_channels = 64, 128 or 256; use ADF_DTYPE_F32 for other widths"; return 1; }
-    adf_handle* h = new adf_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    // the fields of the U-Net config the shared plan / sampler code reads: one waveform channel in and out, no length
-    // constraint, embedding width 4 * channels = dim_out
-    h->cfg.in_channels = 1; h->cfg.out_channels = 1; h->cfg.stride = 1; h->cfg.num_layers = 0; h->cfg.channels = c.dim_out / 4;
-    h->cfg.dtype = c.dtype; h->cfg.resnet_groups = 1;
-    if (hipGetDevice(&h->device) != hipSuccess) { g_create_error = "adf_wavenet_create: hipGetDevice failed"; delete h; return 1; }
-    h->bf16 = c.dtype == ADF_DTYPE_BF16;
-    h->esz = h->bf16 ? 2 : 4;
-    h->kc = kRowBytes / h->esz;
-    h->wn = new WnW();
-    h->wn->cfg = c;
-    if (wn_build_weights(h)) { g_create_error = h->err; adf_destroy(h); return 1; }
-    *out = h;
-    return 0;
-}
-
-int adf_adm_create(const adf_adm_config* cfg, adf_handle** out) {
-    if (!cfg || !out) { g_create_error = "adf_adm_create: null argument"; return 1; }
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "adf_adm_create: no HIP device available"; return 1; }
-    const adf_adm_config& c = *cfg;
-    const int kc = c.dtype == ADF_DTYPE_BF16 ? 64 : 32;
-    if (c.dtype != ADF_DTYPE_F32 && c.dtype != ADF_DTYPE_BF16) { g_create_error = "adf_adm_create: bad dtype"; return 1; }
-    if (c.n_mult < 1 || c.n_mult > ADF_ADM_MAX_LEVELS || c.num_res_blocks < 1 || c.n_attention_ds < 0 || c.n_attention_ds > ADF_ADM_MAX_LEVELS) { g_create_error = "adf_adm_create: bad level / block counts"; return 1; }
-    if (c.model_channels < 32 || c.model_channels % 32 || c.model_channels % kc || c.model_channels > 256) { g_create_error = "adf_adm_create: model_channels must be a multiple of 32 (fp32) / 64 (bf16), at most 256"; return 1; }
-    if (c.in_channels < 1 || c.out_channels < 1 || c.out_channels > 4) { g_create_error = "adf_adm_create: in_channels >= 1, 1 <= out_channels <= 4"; return 1; }
-    if (c.num_classes < 0) { g_create_error = "adf_adm_create: num_classes must be >= 0"; return 1; }
-    for (int i = 0; i < c.n_mult; ++i) if (c.channel_mult[i] < 1) { g_create_error = "adf_adm_create: bad channel_mult"; return 1; }
-    adf_handle* h = new adf_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    // the fields of the U-Net config the shared plan / sampler code reads (embedding width 4 * channels = 4 * model_channels)
-    h->cfg.in_channels = c.in_channels; h->cfg.out_channels = c.out_channels; h->cfg.stride = 1; h->cfg.num_layers = 0;
-    h->cfg.channels = c.model_channels; h->cfg.dtype = c.dtype; h->cfg.resnet_groups = 32;
-    if (hipGetDevice(&h->device) != hipSuccess) { g_create_error = "adf_adm_create: hipGetDevice failed"; delete h; return 1; }
-    h->bf16 = c.dtype == ADF_DTYPE_BF16;
-    h->esz = h->bf16 ? 2 : 4;
-    h->kc = kRowBytes / h->esz;
-    h->adm = new AdmW();
-    h->adm->cfg = c;
-    if (adm_build_weights(h)) { g_create_error = h->err; adf_destroy(h); return 1; }
-    *out = h;
-    return 0;
-}
-
-int adf_unet2d_create(const adf_unet2d_config* cfg, adf_handle** out) {
-    if (!cfg || !out) { g_create_error = "adf_unet2d_create: null argument"; return 1; }
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { g_create_error = "adf_unet2d_create: no HIP device available"; return 1; }
-    const adf_unet2d_config& c = *cfg;
-    auto bad = [](const char* m) { g_create_error = std::string("adf_unet2d_create: ") + m; return 1; };
-    if (c.dtype != ADF_DTYPE_F32) return bad("only the exact-fp32 mode (ADF_DTYPE_F32) is built for this net");
-    if (c.n_levels < 1 || c.n_levels > ADF_U2D_MAX_LEVELS || c.num_resnet_blocks < 1) return bad("bad level / block counts");
-    if (c.n_init_kernels < 1 || c.n_init_kernels > ADF_U2D_MAX_INIT_KERNELS) return bad("1 to 4 cross-embed kernel sizes");
-    if (c.channels < 1 || c.channels_out < 1 || c.channels_out > 4) return bad("channels >= 1, 1 <= channels_out <= 4");
-    if (c.dim % 32 || c.dim < 32 || c.dim > 1024 || c.cond_dim < 1 || c.cond_dim > 512 || c.resnet_groups < 1 || c.attn_heads < 1) return bad("bad widths");
-    if (c.num_classes < 0 || (c.num_classes > 0 && (c.cond_dim != c.dim || c.dim > 512))) return bad("class conditioning needs cond_dim == dim <= 512");
-    if (c.learned_sinu_pos_emb_dim < 2 || c.learned_sinu_pos_emb_dim % 2 || c.num_time_tokens < 1) return bad("bad time embedding widths");
-    if (c.layer_attns_depth < 1 || c.layer_mid_attns_depth < 1 || !(c.ff_mult > 0.0)) return bad("bad transformer settings");
-    for (int i = 0; i < c.n_levels; ++i) {
-        const int w = c.dim * c.dim_mults[i];
-        if (c.dim_mults[i] < 1 || w > 512 || w % c.resnet_groups) return bad("level widths must be at most 512 (a skip concat feeds a conv of at most 1024 channels) and multiples of resnet_groups");
-        if (c.layer_attns[i] || c.attend_at_middle) {
-            if (w % c.attn_heads) return bad("attention widths must divide into the heads");
-        }
-    }
-    for (int i = 0; i < c.n_init_kernels; ++i)
-        if (c.init_kernel_sizes[i] < 1 || !(c.init_kernel_sizes[i] & 1) || (i && c.init_kernel_sizes[i] < c.init_kernel_sizes[i - 1])) return bad("cross-embed kernel sizes must be odd and sorted");
-    adf_handle* h = new adf_handle();
-    memset(&h->cfg, 0, sizeof(h->cfg));
-    // the fields of the U-Net config the shared plan / sampler code reads (time embedding width 4 * channels = 4 * cond_dim; label width = dim)
-    h->cfg.in_channels = c.channels; h->cfg.out_channels = c.channels_out; h->cfg.stride = 1; h->cfg.num_layers = 0;
-    h->cfg.channels = c.cond_dim; h->cfg.dtype = c.dtype; h->cfg.resnet_groups = c.resnet_groups; h->cfg.num_classes = c.num_classes;
-    if (hipGetDevice(&h->device) != hipSuccess) { g_create_error = "adf_unet2d_create: hipGetDevice failed"; delete h; return 1; }
-    h->bf16 = false;
-    h->esz = 4;
-    h->kc = kRowBytes / h->esz;
-    h->u2d = new U2dW();
-    U2dW& u = *h->u2d;
-    u.cfg = c;
-    u.init_dim = c.dim; u.tcd = 4 * c.cond_dim;
-    // CrossEmbedLayer's split of init_dim over the sorted kernel sizes (:268-272): init_dim / 2, / 4, ..., the remainder to the largest
-    for (int i = 0; i + 1 < c.n_init_kernels; ++i) u.ce_off[i + 1] = u.ce_off[i] + (c.dim >> (i + 1));
-    u.ce_off[c.n_init_kernels] = c.dim;
-    for (int i = 0; i < c.n_init_kernels; ++i)
-        if (u.ce_off[i + 1] - u.ce_off[i] < 4 || (u.ce_off[i + 1] - u.ce_off[i]) % 4) { g_create_error = "adf_unet2d_create: every cross-embed slice must be a multiple of 4 channels"; adf_destroy(h); return 1; }
-    if (u2d_build_weights(h)) { g_create_error = h->err; adf_destroy(h); return 1; }
-    *out = h;
-    return 0;
-}
-
 int adf_set_image_shape(adf_handle* h, int H, int W) {
-    if (!h || (!h->adm && !h->u2d)) return h ? fail(h, "adf_set_image_shape: not a UNetModel / UNet2dBase handle") : 1;
+    if (!h || !h->net->image) return h ? fail(h, "adf_set_image_shape: not a UNetModel / UNet2dBase handle") : 1;
     if (H < 1 || W < 1) return fail(h, "adf_set_image_shape: bad shape");
-    if (h->u2d) { h->u2d->H = H; h->u2d->W = W; return 0; }
-    h->adm->H = H; h->adm->W = W;
+    h->net->H = H; h->net->W = W;
     return 0;
 }
 
@@ -234,9 +115,6 @@ void adf_destroy(adf_handle* h) {
     if (h->ev_in) (void)hipEventDestroy(h->ev_in);
     if (h->ev_out) (void)hipEventDestroy(h->ev_out);
     if (h->gstream) (void)hipStreamDestroy(h->gstream);
-    delete h->wn;
-    delete h->adm;
-    delete h->u2d;
     delete h;
 }
 
@@ -266,7 +144,7 @@ int adf_load_weight(adf_handle* h, const char* name, const float* dev, int64_t n
         if (const char* e = launch_permute_qkv_rows(dev, (float*)sl.frag, sl.f, sl.cout / (3 * sl.f), sl.cin, s)) return fail(h, e);
         if (const char* e = launch_pack_weight((const float*)sl.frag, sl.dst, h->gemm_dtype(), 0, sl.cout, sl.cin, sl.K, 0, sl.n_offset, sl.n_pad, sl.nchunk, s))
             return fail(h, e);
-    } else if (sl.kind == 6 && h->u2d) {     // UNet2dBase: a load-time transform into an fp32 scratch copy (adf_unet2d.h), then the usual packing
+    } else if (sl.kind == 6) {               // UNet2dBase: a load-time transform into an fp32 scratch copy (adf_unet2d.h), then the usual packing
         if (const char* e = launch_u2d_weight_transform(dev, (float*)sl.frag, sl.xmode, sl.cout, sl.cin, sl.K, sl.xc0, sl.xscale, s)) return fail(h, e);
         if (const char* e = launch_pack_weight((const float*)sl.frag, sl.dst, h->gemm_dtype(), 0, sl.cout, sl.cin, sl.K, 0, sl.n_offset, sl.n_pad, sl.nchunk, s))
             return fail(h, e);
@@ -285,7 +163,7 @@ int adf_load_weight(adf_handle* h, const char* name, const float* dev, int64_t n
         }
     }
     sl.loaded = true;
-    if (h->wn) h->wn->packed = false;      // the effective weights (v * g / ||v||) are rebuilt before the next pass
+    h->net->weight_loaded();
     return 0;
 }
 
@@ -328,14 +206,14 @@ int adf_set_condition(adf_handle* h, const int64_t* classes_dev, int B, int null
         h->cond_cap = B;
     }
     if (hipMemcpyAsync(h->cond_classes, classes_dev, (size_t)B * 8, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "class label copy failed");
-    const adf_net_config& c = h->cfg;
-    if (const char* e = launch_class_embed(h->cond_classes, h->adm ? h->adm->cfg.num_classes : c.num_classes, null_labels ? 1 : 0, h->lab_emb, h->lab_null, h->lab_lnw, h->lab_lnb,
-                                           h->lab_w1, h->lab_b1, h->lab_w2, h->lab_b2, c.channels, h->cdim, h->cond_emb, B + 1, s))
+    const NetDims& c = h->net->dims;
+    if (const char* e = launch_class_embed(h->cond_classes, c.num_classes, null_labels ? 1 : 0, h->lab_emb, h->lab_null, h->lab_lnw, h->lab_lnb,
+                                           h->lab_w1, h->lab_b1, h->lab_w2, h->lab_b2, c.label_in, h->cdim, h->cond_emb, B + 1, s))
         return fail(h, e);
     // class part of every FiLM projection: columns [tdim, tdim + cdim) of the concatenated weight, no bias (it is in the time part)
-    // (not for the ADM net: its embeddings are ADDED before the SiLU of emb_layers, unet2d_oai.py:621-623, so nothing separates)
-    if (!h->adm && !h->u2d)      // (nor for UNet2dBase: t + label embedding, then each block's SiLU -> Linear, unet2d.py:902-908)
-        if (const char* e = launch_film(h->cond_emb, h->cdim, h->film_w, 4 * c.channels + h->cdim, 4 * c.channels, nullptr, h->cond_film, B + 1,
+    // (not where the embeddings are ADDED before the projections, Net::class_in_temb: nothing separates)
+    if (!h->net->class_in_temb)
+        if (const char* e = launch_film(h->cond_emb, h->cdim, h->film_w, c.temb + h->cdim, c.temb, nullptr, h->cond_film, B + 1,
                                         h->film_total, s))
             return fail(h, e);
     h->cond_on = true; h->cond_B = B; h->cond_scale = cond_scale;
@@ -400,13 +278,14 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
     if (!desc || !sigmas_host || n_sigmas < 1) return fail(h, "adf_sampler_run: bad arguments");
     Plan* p;
     if (get_plan(h, B, L, s, &p)) return 1;
-    const long long n = (long long)B * h->cfg.out_channels * L;
-    if (h->cfg.in_channels != h->cfg.out_channels) return fail(h, "sampler needs in_channels == out_channels");
+    const NetDims& nd = h->net->dims;
+    const long long n = (long long)B * nd.out_channels * L;
+    if (nd.in_channels != nd.out_channels) return fail(h, "sampler needs in_channels == out_channels");
     if (h->cdim > 0) {
         if (!h->cond_on || h->cond_B != B) return fail(h, "class-conditional network: call adf_set_condition with the labels of this batch first");
         if (h->cond_scale != 1.0f && ensure_cfg_buffers(h, p)) return 1;
     }
-    if (h->unclipped() && !h->u2d && ensure_cfg_buffers(h, p)) return 1;     // unclipped estimate off UNet2dBase: raw pass + combine (denoise_io)
+    if (h->unclipped() && !h->net->unclipped_epilogue && ensure_cfg_buffers(h, p)) return 1;     // unclipped estimate without a mode 2 epilogue: raw pass + combine (denoise_io)
     if (h->dyn_q > 0.0f) {                               // buffers of the dynamic threshold: allocated before any capture starts
         if (ensure_cfg_buffers(h, p)) return 1;
         if (!p->dyn_scale) {
@@ -459,12 +338,12 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
             (void)hipDeviceSynchronize();
             drop_graphs(p);
             dfree(h, p->coef_all, (size_t)p->pre_cap * 4 * 4, p);
-            dfree(h, p->temb_all, (size_t)p->pre_cap * 4 * h->cfg.channels * 4, p);
+            dfree(h, p->temb_all, (size_t)p->pre_cap * nd.temb * 4, p);
             dfree(h, p->film_all, (size_t)p->pre_cap * h->film_total * 4, p);
             p->pre_cap = 0;
         }
         p->coef_all = (float*)dalloc(h, (size_t)n_eval * 4 * 4, p);
-        p->temb_all = (float*)dalloc(h, (size_t)n_eval * 4 * h->cfg.channels * 4, p);
+        p->temb_all = (float*)dalloc(h, (size_t)n_eval * nd.temb * 4, p);
         p->film_all = (float*)dalloc(h, (size_t)n_eval * h->film_total * 4, p);
         if (!p->coef_all || !p->temb_all || !p->film_all) return fail(h, "device allocation failed for the per-run sigma table");
         p->pre_cap = n_eval;
@@ -473,31 +352,10 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
     // evaluations in three launches
     auto sigma_table = [&](hipStream_t st) -> int {
         if (n_eval == 0) return 0;
-        const adf_net_config& cfg = h->cfg;
         if (const char* e = launch_edm_coef_list(eval_sigmas.data(), n_eval, h->precond_for(desc->sigma_data), p->coef_all, st)) return fail(h, e);
-        if (h->wn) {
-            const adf_wavenet_config& wc = h->wn->cfg;
-            if (const char* e = launch_wn_step_embed(p->coef_all + 1, 4, n_eval, h->wn->fc1w, h->wn->fc1b, h->wn->fc2w, h->wn->fc2b, wc.dim_in,
-                                                     wc.dim_mid, wc.dim_out, p->temb_all, st))
-                return fail(h, e);
-        } else if (h->adm) {
-            const AdmW& am = *h->adm;
-            if (const char* e = launch_adm_time_embed(p->coef_all + 1, 4, n_eval, am.cfg.model_channels, am.t_w1, am.t_b1, am.t_w2, am.t_b2,
-                                                      4 * am.cfg.model_channels, p->temb_all, st))
-                return fail(h, e);
-        } else if (h->u2d) {
-            const U2dW& u = *h->u2d;
-            if (const char* e = launch_u2d_time_embed(p->coef_all + 1, 4, n_eval, u.fourier, u.cfg.learned_sinu_pos_emb_dim / 2, u.t_w1, u.t_b1, u.t_w2, u.t_b2,
-                                                      u.tcd, p->temb_all, st))
-                return fail(h, e);
-        } else {
-            TimeEmbedArgs te;
-            te.t = p->coef_all + 1; te.t_stride = 4; te.nb = n_eval; te.ch = cfg.channels;
-            te.fourier = h->fourier; te.w1 = h->t_w1; te.b1 = h->t_b1; te.w2 = h->t_w2; te.b2 = h->t_b2; te.temb = p->temb_all;
-            if (const char* e = launch_time_embed(te, st)) return fail(h, e);
-        }
-        if ((h->adm || h->u2d) && h->cdim > 0) return 0;       // per-sample FiLM rows (time + class embedding): projected inside each pass
-        if (const char* e = launch_film(p->temb_all, 4 * cfg.channels, h->film_w, 4 * cfg.channels + h->cdim, 0, h->film_b, p->film_all, n_eval,
+        if (const char* e = h->net->time_embed(p->coef_all + 1, 4, n_eval, p->temb_all, st)) return fail(h, e);
+        if (h->per_sample_film()) return 0;                    // per-sample FiLM rows (time + class embedding): projected inside each pass
+        if (const char* e = launch_film(p->temb_all, nd.temb, h->film_w, nd.temb + h->cdim, 0, h->film_b, p->film_all, n_eval,
                                         h->film_total, st))
             return fail(h, e);
         return 0;

@@ -1,12 +1,14 @@
 // Internals shared by the translation units behind the C ABI (include/audiodiffuser_amd.h): the handle, the per-(B, L) workspace
 // ("plan"), the weight registry, the network walker.  Round 3 split of what was one 2,400-line adf_api.hip:
-//   adf_api.hip            handle life cycle, weights, workspaces, the extern "C" entry points
-//   adf_net_unet1d.hip     UNet1dBase: registry + walk (unet1d.py:771-816)
-//   adf_net_wavenet.hip    WaveNetNoise (wavenet.py:153-180)
-//   adf_net_adm.hip        ADM UNetModel (unet2d_oai.py:382-635)
-//   adf_net_unet2d.hip     Imagen-style UNet2dBase (unet2d.py:622-972), exact fp32
+//   adf_api.hip            handle life cycle, weights, workspaces, the extern "C" entry points every network shares
+//   adf_net_unet1d.hip     Unet1dNet: UNet1dBase (unet1d.py:771-816): adf_create, registry, the 1-D walker and its walk
+//   adf_net_wavenet.hip    WavenetNet (declared in adf_net_wavenet.h): WaveNetNoise (wavenet.py:153-180): adf_wavenet_create, registry, walk
+//   adf_net_adm.hip        AdmNet: ADM UNetModel (unet2d_oai.py:382-635): adf_adm_create, registry, walk
+//   adf_net_unet2d.hip     Unet2dNet: Imagen-style UNet2dBase (unet2d.py:622-972), exact fp32: adf_unet2d_create, registry, walk
+//   adf_walk2d.h           what the two 2-D walks share: fine GroupNorm statistics, the conv launch, the conditioning prologue
 //   adf_sampler.hip        denoise wrappers and the sampler state machines (sampler_edm.py, stochastic_sampler_edm.py)
 //   adf_bench_replay.hip   adf_bench_* instrumentation
+// A handle owns one Net (below).  This header, adf_api.hip and adf_sampler.hip know a network only through that interface.
 #pragma once
 #include "../../include/audiodiffuser_amd.h"
 #include "adf_gemm.h"
@@ -24,6 +26,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -39,21 +42,6 @@ struct ConvW {
     float* bias = nullptr;
     int cout = 0, cin = 0, K = 0, n = 0, n_pad = 0, nchunk = 0, taps = 0, f = 0;
 };
-struct ResW {
-    int cin = 0, cout = 0, film_off = 0;
-    float *g1w = nullptr, *g1b = nullptr, *g2w = nullptr, *g2b = nullptr;
-    ConvW c1, c2, cr;
-    bool has_res = false;
-};
-struct TrW {
-    int c = 0, mid = 0;
-    float *lnw = nullptr, *lnb = nullptr, *g0 = nullptr, *g3 = nullptr;
-    ConvW qkv, proj, ff1, ff2;
-};
-struct DownW { ConvW down; std::vector<ResW> blocks; bool attn = false; TrW tr; int factor = 1, cin = 0, cout = 0; };
-// up3: the same transposed conv as a 3-tap stride-1 conv with f * cout output columns (phase-major; [B][f L][cout] IS [B][L][f cout] in memory) -- the shape
-// conv_gemm_rb_kernel<.., RAW> is written for; packed beside `up` when the factor is even and f * cout is 128 or 256 (bf16 mode)
-struct UpW { std::vector<ResW> blocks; bool attn = false; TrW tr; ConvW up; ConvW up3; int factor = 1, cin = 0, cout = 0; bool nearest = false; };
 
 struct Slot {
     int kind = 0;  // 0 = fp32 copy, 1 = pack conv/linear, 2 = pack transposed conv
@@ -69,74 +57,6 @@ struct Slot {
 
 struct Act { void* p = nullptr; int C = 0, L = 0; double* stats = nullptr; };
 struct TapRec { std::string name; void* p; int C, L; int f32 = 0; float scale = 1.0f; };   // f32: an fp32 buffer whatever the storage mode
-
-// WaveNetNoise (wavenet.py:153-180): a weight-normed conv keeps the state-dict tensors (bias, 0-dim g, v) in fp32 and a packed
-// GEMM operand of the effective weight v * g / ||v||, rebuilt when a tensor was (re)loaded
-struct WnConv {
-    float *bias = nullptr, *g = nullptr, *v = nullptr;
-    void* packed = nullptr;
-    int cout = 0, cin = 0, K = 0;
-};
-// ADM-style 2-D U-Net (unet2d_oai.py:382-635): the module list of UNetModel.__init__ as data
-struct AdmRes { int cin = 0, cout = 0, film_off = 0; float *g1w = nullptr, *g1b = nullptr, *g2w = nullptr, *g2b = nullptr; ConvW c1, c2, skip; bool has_skip = false;
-                int updown = 0; };        // 1: ResBlock(up=True), 2: ResBlock(down=True) (resblock_updown, unet2d_oai.py:197-207, :249-254)
-struct AdmAttn { int c = 0, heads = 0; float *gw = nullptr, *gb = nullptr; ConvW qkv, proj; float* qkv_tmp = nullptr; };
-struct AdmLayer { int kind; int idx; };       // kind: 0 input conv, 1 ResBlock, 2 AttentionBlock, 3 Downsample (conv), 4 Upsample (conv), 5 average pool, 6 nearest x 2
-struct AdmW {
-    adf_adm_config cfg;
-    int H = 0, W = 0;                    // image shape of the calls that follow (adf_set_image_shape)
-    std::vector<AdmRes> res;
-    std::vector<AdmAttn> attn;
-    std::vector<ConvW> resample;
-    std::vector<std::vector<AdmLayer>> input_blocks, output_blocks;
-    std::vector<AdmLayer> middle;
-    std::vector<int> skip_ch;            // channels of the input-block outputs, in push order
-    float *in_w = nullptr, *in_b = nullptr, *t_w1 = nullptr, *t_b1 = nullptr, *t_w2 = nullptr, *t_b2 = nullptr;
-    float *out_gw = nullptr, *out_gb = nullptr, *out_w = nullptr, *out_b = nullptr;
-    int input_ch = 0, final_ch = 0;
-    int fg = 4;                          // channels per fine statistics group: gcd of every GroupNorm group size of the net (incl. the skip concats)
-};
-
-// Imagen-style UNet2dBase (unet2d.py:622-972): the module tree of the memory-efficient layout as data
-struct U2dRes {
-    int cin = 0, cout = 0, skip_c = 0, film_off = 0;   // skip_c: channels of the (scaled) skip half of the input (up blocks), 0 otherwise
-    float *g1w = nullptr, *g1b = nullptr, *g2w = nullptr, *g2b = nullptr;
-    ConvW c1, c2, res;
-    bool has_res = false, gca = false;
-    int gca_hid = 0;
-    float *gk_w = nullptr, *gk_b = nullptr, *gn0_w = nullptr, *gn0_b = nullptr, *gn2_w = nullptr, *gn2_b = nullptr;
-};
-struct U2dTrLayer { ConvW qkv, out, ff1, ff2; float *g0 = nullptr, *g3 = nullptr; };
-struct U2dTr { int c = 0, hid = 0, heads = 0; std::vector<U2dTrLayer> layers; float* norm_g = nullptr; };
-struct U2dLevel {
-    int din = 0, dout = 0;
-    ConvW down;                          // Downsample's 1x1 conv over unshuffled channels, packed as a 3x3 / stride-2 conv (slot kind 6)
-    std::vector<U2dRes> down_rb, up_rb;  // [0] = the block without a gate (ds_block.1 / us_block.0), then the gated ones
-    bool attn = false;
-    U2dTr down_tr, up_tr;
-    ConvW up;                            // PixelShuffleUpsample's 1x1 conv dout -> 4 din
-};
-struct U2dW {
-    adf_unet2d_config cfg;
-    int H = 0, W = 0;                    // image shape of the calls that follow (adf_set_image_shape)
-    int init_dim = 0, tcd = 0, fg = 4;
-    int ce_off[5] = {0};
-    float *ce_w[4] = {nullptr}, *ce_b[4] = {nullptr};
-    float *fourier = nullptr, *t_w1 = nullptr, *t_b1 = nullptr, *t_w2 = nullptr, *t_b2 = nullptr;
-    U2dRes init_rb, mid1, mid2, final_rb;
-    U2dTr mid_tr;
-    std::vector<U2dLevel> lv;
-    float *out_w = nullptr, *out_b = nullptr;
-};
-
-struct WnW {
-    adf_wavenet_config cfg;
-    WnConv in, sp;
-    std::vector<WnConv> dil, outp;
-    float *fc1w = nullptr, *fc1b = nullptr, *fc2w = nullptr, *fc2b = nullptr, *out_w = nullptr, *out_b = nullptr;
-    double* sumsq = nullptr;             // scratch of the norm reduction
-    bool packed = false;
-};
 struct RbRec { std::string name; GemmArgs g1, g2; int cin, cout, L; };
 
 struct Plan {
@@ -171,13 +91,52 @@ struct Plan {
 constexpr size_t kMaxGraphsPerPlan = 8;
 constexpr size_t kMaxPlans = 4;      // (B, L) workspaces kept per handle; the least recently used one is released beyond that
 
+struct FwdIO {
+    const float* x = nullptr; float* out = nullptr;
+    const float* t = nullptr; int t_stride = 0; int nb = 0;
+    const float* coef = nullptr; int coef_bstride = 0; const float* x_noisy = nullptr;
+    int mode = 0;                                          // 0: raw network output; 1: clamp(c_skip x_noisy + c_out F, -1, 1); 2: the same unclipped (UNet2dBase only)
+    const float* film2 = nullptr; int film2_bstride = 0;   // class part of the FiLM projections (rows of adf_handle::cond_film)
+    const float* film_pre = nullptr;                       // this evaluation's row of Plan::film_all: sigma embedding + FiLM already computed
+    const float* temb_pre = nullptr;                       // this evaluation's row of Plan::temb_all (class-conditional ADM net: the FiLM rows are per sample)
+    bool null_cond = false;                                // class-conditional ADM net: every sample takes the null class embedding (guidance branch)
+};
+
+// What the shared plan, condition and sampler code reads of a network.  The create call fills it once; nothing else writes it.
+struct NetDims {
+    int in_channels = 0, out_channels = 0;
+    int length_multiple = 1;            // the length argument L must be a multiple of this (UNet1dBase: its total down-sampling factor)
+    int temb = 0;                       // width of the time embedding: a row of Plan::temb / temb_all
+    int label_in = 0, num_classes = 0;  // LabelEmbedder: width of its embedding table, number of labels (0 = no class conditioning)
+    int stat_groups = 1;                // GroupNorm groups per sample in one Walker::alloc_stats slab
+};
+
+// One network behind the C ABI: what the shared code asks of it.  One implementation per adf_net_*.hip.
+struct Net {
+    NetDims dims;
+    // the class embedding is added to the time embedding before the FiLM projections, so the FiLM rows are per sample (UNetModel, unet2d_oai.py:621-623;
+    // UNet2dBase, unet2d.py:902-908); false: the class columns are projected on their own into adf_handle::cond_film (UNet1dBase, unet1d.py:272)
+    bool class_in_temb = false;
+    bool unclipped_epilogue = false;    // the last kernel has the FwdIO mode 2 epilogue (only UNet2dBase)
+    // inputs are images [B][C][H][W]: adf_set_image_shape gives the shape behind the length argument L = H * W of the calls that follow
+    bool image = false;
+    int H = 0, W = 0;
+    virtual ~Net() {}
+    virtual int build_weights(adf_handle* h) = 0;                        // the registry, in state_dict order
+    virtual int check_image(adf_handle* h, int L) { (void)h; (void)L; return 0; }      // image nets: (H, W) against L and the levels, before a plan
+    virtual void weight_loaded() {}                                      // a tensor was (re)loaded ...
+    virtual int prepare(adf_handle* h, hipStream_t s) { (void)h; (void)s; return 0; }   // ... and what that needs before the next pass
+    virtual int forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) = 0;
+    // n rows of the time / sigma embedding ([n][dims.temb]) from t[i * t_stride]
+    virtual const char* time_embed(const float* t, int t_stride, int n, float* temb, hipStream_t s) = 0;
+};
 
 }  // namespace adf_api
 
 using namespace adf_api;      // (this header is private to the translation units behind the C ABI)
 
 struct adf_handle {
-    adf_net_config cfg;
+    std::unique_ptr<Net> net;
     int device = 0;                     // the device that was current at adf_create: every entry point runs on it
     unsigned long long use_clock = 0;
     bool bf16 = false;
@@ -189,13 +148,13 @@ struct adf_handle {
     int64_t bytes = 0;
     std::vector<std::string> names;
     std::map<std::string, Slot> slots;
-    float *to_in_w = nullptr, *to_out_w = nullptr, *fourier = nullptr, *t_w1 = nullptr, *t_b1 = nullptr, *t_w2 = nullptr,
-          *t_b2 = nullptr, *film_w = nullptr, *film_b = nullptr;
+    float *film_w = nullptr, *film_b = nullptr;      // every FiLM projection of the network, concatenated: [film_total][temb (+ cdim)], [film_total]
     int film_total = 0;
     // class conditioning (LabelEmbedder) and the state set by adf_set_condition
     float *lab_null = nullptr, *lab_emb = nullptr, *lab_lnw = nullptr, *lab_lnb = nullptr, *lab_w1 = nullptr, *lab_b1 = nullptr,
           *lab_w2 = nullptr, *lab_b2 = nullptr;
-    int cdim = 0;                       // width of the class embedding (4 * channels) or 0
+    int cdim = 0;                       // width of the class embedding (Registrar::label_embedder) or 0
+    bool per_sample_film() const { return net->class_in_temb && cdim > 0; }      // FiLM rows differ per sample: projected inside each pass
     bool cond_on = false;
     int cond_B = 0;
     float cond_scale = 1.0f;
@@ -207,17 +166,10 @@ struct adf_handle {
     float* cond_emb = nullptr;          // [cond_B + 1][cdim], last row = null embedding
     float* cond_film = nullptr;         // [cond_B + 1][film_total]: class part of every FiLM projection
     int cond_cap = 0;
-    std::vector<DownW> downs;
-    ResW mid_pre, mid_post;
-    TrW mid_tr;
-    std::vector<UpW> ups;
-    // (B, L, H): H = image height of a UNetModel handle (W = L / H), 0 otherwise -- two image shapes with equal H * W must not share
+    // (B, L, H): H = image height of an image net (W = L / H), 0 otherwise -- two image shapes with equal H * W must not share
     // a workspace: captured graphs and tap shapes carry the conv2d geometry
     std::map<std::tuple<int, int, int>, Plan*> plans;
     Plan* last_plan = nullptr;
-    WnW* wn = nullptr;                  // non-null: the handle is a WaveNetNoise (adf_wavenet_create), not a UNet1dBase
-    AdmW* adm = nullptr;                // non-null: the handle is an ADM-style UNetModel (adf_adm_create)
-    U2dW* u2d = nullptr;                // non-null: the handle is an Imagen-style UNet2dBase (adf_unet2d_create)
     // graphs are captured and replayed on a library-owned stream (the caller's stream may be the legacy
     // default stream, which cannot be captured); it is fenced against the caller's stream with events
     hipStream_t gstream = nullptr;
@@ -314,87 +266,35 @@ struct Registrar {
         reg_pack(pre + ".weight", w, cout, cin, K, 0, cout, false, 0);
         if (bias) w.bias = reg_f32(pre + ".bias", cout);
     }
-    // Strided Conv1d (kernel f*km + 1, stride f, pad f*(km/2)) folded to a stride-1 conv with km + 1 taps over
-    // f*cin channels: the contiguous [L][cin] input is the same memory as [L/f][f*cin], so the fast stride-1 GEMM
-    // kernels apply unchanged (the folded taps beyond the real kernel length are zero weights)
-    void conv_folded(const std::string& pre, ConvW& w, int cout, int cin, int K, int f) {
-        w.cin = f * cin; w.K = K; w.f = f;
-        w.taps = (K - 1) / f + 1;
-        w.n = cout; w.n_pad = round_up(cout, 32);
-        w.nchunk = ceil_div(f * cin, h->kc);
-        w.w = dalloc(h, ((size_t)w.nchunk * w.taps * w.n_pad + (size_t)kTapGroup * (w.n_pad + 128)) * kRowBytes);
-        if (!w.w) { ok = false; return; }
-        w.cout = cout;
-        Slot s; s.kind = 3; s.dst = w.w; s.numel = (int64_t)cout * cin * K;
-        s.cout = cout; s.cin = cin; s.K = K; s.f = f; s.n_offset = 0; s.n_pad = w.n_pad; s.nchunk = w.nchunk; s.taps = w.taps;
-        h->names.push_back(pre + ".weight"); h->slots[pre + ".weight"] = s;
-        w.bias = reg_f32(pre + ".bias", cout);
+    // LabelEmbedder(num_classes, width_in, width_out) (conditioner.py:64-90): sets the handle's lab_* tensors and cdim
+    void label_embedder(int width_in, int width_out, int num_classes) {
+        h->cdim = width_out;
+        h->lab_null = reg_f32("label_conditioner.null_classes_emb", width_in);
+        h->lab_emb = reg_f32("label_conditioner.label_emb.weight", (int64_t)num_classes * width_in);
+        h->lab_lnw = reg_f32("label_conditioner.class_to_cond.0.weight", width_in);
+        h->lab_lnb = reg_f32("label_conditioner.class_to_cond.0.bias", width_in);
+        h->lab_w1 = reg_f32("label_conditioner.class_to_cond.1.weight", (int64_t)width_out * width_in);
+        h->lab_b1 = reg_f32("label_conditioner.class_to_cond.1.bias", width_out);
+        h->lab_w2 = reg_f32("label_conditioner.class_to_cond.3.weight", (int64_t)width_out * width_out);
+        h->lab_b2 = reg_f32("label_conditioner.class_to_cond.3.bias", width_out);
     }
-    void resblock(const std::string& pre, ResW& r, int cin, int cout, int temb) {
-        r.cin = cin; r.cout = cout;
-        r.film_off = h->film_total;
-        h->film_total += 2 * cout;
-        // FiLM weights are registered later (one concatenated matrix), remember the order via names
-        film_names.push_back({pre, r.film_off, 2 * cout});
-        r.g1w = reg_f32(pre + ".block1.groupnorm.weight", cin);
-        r.g1b = reg_f32(pre + ".block1.groupnorm.bias", cin);
-        conv(pre + ".block1.project", r.c1, cout, cin, 3, true);
-        r.g2w = reg_f32(pre + ".block2.groupnorm.weight", cout);
-        r.g2b = reg_f32(pre + ".block2.groupnorm.bias", cout);
-        conv(pre + ".block2.project", r.c2, cout, cout, 3, true);
-        r.has_res = cin != cout;
-        if (r.has_res) conv(pre + ".to_out", r.cr, cout, cin, 1, true);
-        if (h->bf16 && (cout == 256 || cout == 128) && (cin == cout || cin == 2 * cout)) {   // fragment-major copies: adf_resblock_small.h, adf_gemm_tile.h
-            const std::pair<const char*, ConvW*> m[] = {{".block1.project.weight", &r.c1}, {".block2.project.weight", &r.c2}, {".to_out.weight", &r.cr}};
-            for (const auto& kv : m) {
-                ConvW* w = kv.second;
-                if (!w->w) continue;
-                w->wfrag = dalloc(h, (size_t)w->nchunk * w->taps * w->n_pad * kRowBytes);
-                if (!w->wfrag) { ok = false; return; }
-                h->slots[pre + kv.first].frag = w->wfrag;
-            }
-        }
-        (void)temb;
-    }
-    void transformer(const std::string& pre, TrW& t, int c, int mult) {
-        t.c = c; t.mid = c * mult;
-        t.lnw = reg_f32(pre + ".norm.weight", c);
-        t.lnb = reg_f32(pre + ".norm.bias", c);
-        reg_pack(pre + ".attention.to_q.weight", t.qkv, c, c, 1, 0, 3 * c, false, 0);
-        reg_pack(pre + ".attention.to_kv.weight", t.qkv, 2 * c, c, 1, c, 3 * c, false, 0);
-        t.qkv.cout = 3 * c;
-        conv(pre + ".attention.to_out", t.proj, c, c, 1, false);
-        t.g0 = reg_f32(pre + ".feed_forward.0.g", c);
-        conv(pre + ".feed_forward.1", t.ff1, t.mid, c, 1, false);
-        t.g3 = reg_f32(pre + ".feed_forward.3.g", t.mid);
-        conv(pre + ".feed_forward.4", t.ff2, c, t.mid, 1, false);
-        if (h->bf16) {
-            for (ConvW* w : {&t.qkv, &t.proj, &t.ff1, &t.ff2}) {
-                w->wfrag = dalloc(h, (size_t)w->nchunk * w->n_pad * kRowBytes);
-                if (!w->wfrag) { ok = false; return; }
-            }
-            const std::pair<const char*, ConvW*> m[] = {{".attention.to_q.weight", &t.qkv}, {".attention.to_kv.weight", &t.qkv},
-                                                       {".attention.to_out.weight", &t.proj}, {".feed_forward.1.weight", &t.ff1},
-                                                       {".feed_forward.4.weight", &t.ff2}};
-            for (const auto& kv : m) h->slots[pre + kv.first].frag = kv.second->wfrag;
-        }
-    }
-    struct FilmName { std::string pre; int off, rows; };
-    std::vector<FilmName> film_names;
 };
 
-
-int build_weights(adf_handle* h);
 // ---- per-(B, L) plan -----------------------------------------------------------------------------
+// What every network's walk uses: the activation and statistics arenas of the plan, the tap list, the first error.
 struct Walker {
     adf_handle* h;
     Plan* p;
     hipStream_t s;
     bool bad = false;
-    const float* film2 = nullptr;       // class part of the FiLM projections for this pass (FwdIO::film2)
-    int film2_bstride = 0;
-    const float* film = nullptr;        // time part: Plan::film, or the evaluation's row of Plan::film_all
 
+    // start of a pass: empty arenas and tap list; the statistics slab zeroed (the kernels accumulate into it)
+    int begin() {
+        p->arena_off = 0; p->stats_off = 0;
+        p->taps.clear(); p->rbs.clear();
+        if (!p->dry && p->stats_bytes && hipMemsetAsync(p->stats, 0, p->stats_bytes, s) != hipSuccess) return fail(h, "hipMemsetAsync(stats) failed");
+        return 0;
+    }
     void check(const char* e) { if (e && !bad) { bad = true; h->err = e; } }
     void* alloc(size_t bytes) {
         bytes = (bytes + 255) & ~(size_t)255;
@@ -405,7 +305,7 @@ struct Walker {
         return p->arena + off;
     }
     double* alloc_stats() {
-        const size_t bytes = ((size_t)p->B * h->cfg.resnet_groups * 2 * sizeof(double) + 255) & ~(size_t)255;
+        const size_t bytes = ((size_t)p->B * h->net->dims.stat_groups * 2 * sizeof(double) + 255) & ~(size_t)255;
         const size_t off = p->stats_off;
         p->stats_off += bytes;
         if (p->dry) return (double*)(uintptr_t)(off + 256);  // non-null marker
@@ -415,248 +315,13 @@ struct Walker {
     Act new_act(int C, int L) { Act a; a.C = C; a.L = L; a.p = alloc((size_t)p->B * L * C * h->esz); return a; }
     void tap(const std::string& name, const Act& a) { p->taps.push_back({name, a.p, a.C, a.L}); }
     bool live() const { return !p->dry && !bad; }
-
-    bool can_fuse_stats(int C) const {
-        if (h->cfg.flags & ADF_FLAG_SEPARATE_GN_STATS) return false;
-        const int G = h->cfg.resnet_groups;
-        if (C % G) return false;
-        const int gs = C / G;
-        return (gs & (gs - 1)) == 0;
-    }
-    double* ensure_stats(Act& t) {
-        if (!t.stats) {
-            t.stats = alloc_stats();
-            if (live()) check(launch_gn_stats(t.p, h->bf16, p->B, t.L, t.C, h->cfg.resnet_groups, t.stats, s));
-        }
-        return t.stats;
-    }
-
-    GemmArgs gemm_base(const Act& out, int lin, int mrows, const ConvW& w) {
-        GemmArgs g;
-        memset(&g, 0, sizeof(g));
-        g.nseg = 1; g.B = p->B; g.lin = lin; g.mrows = mrows; g.n = w.n; g.n_pad = w.n_pad;
-        g.bias0 = w.bias; g.bias_mod = w.n > 0 ? w.n : 1;
-        g.out = out.p; g.out_rows = out.L; g.out_c = out.C;
-        return g;
-    }
-    static GemmSeg seg_of(const Act& x, const Act* skip, const float* ab, float scale1, int act, int taps, int stride, int off0,
-                          int step, const ConvW& w) {
-        GemmSeg sg;
-        memset(&sg, 0, sizeof(sg));
-        sg.src0 = x.p; sg.c0 = x.C;
-        sg.src1 = skip ? skip->p : nullptr; sg.c1 = skip ? skip->C : 0;
-        sg.ab = ab; sg.scale1 = scale1; sg.act = act;
-        sg.taps = taps; sg.stride = stride; sg.off0 = off0; sg.step = step;
-        sg.w = w.w; sg.wfrag = w.wfrag; sg.nchunk = w.nchunk;
-        return sg;
-    }
-    void run_gemm(GemmArgs& g, Act& out, bool want_stats) {
-        const bool ask = want_stats && can_fuse_stats(out.C);      // also for the phase-scattered transposed convs
-        if (ask) {
-            out.stats = alloc_stats();
-            g.stats = out.stats; g.stats_groups = h->cfg.resnet_groups;
-        }
-        if (live()) {
-            bool fused = false;
-            check(launch_conv_gemm(g, h->gemm_dtype(), s, &fused));
-            // the launcher may decline (tile shape / group size): fill the same buffer with the separate pass
-            if (ask && !fused) check(launch_gn_stats(out.p, h->bf16, p->B, out.L, out.C, h->cfg.resnet_groups, out.stats, s));
-        }
-    }
-
-    Act linear(const Act& x, const ConvW& w, const void* res, int gelu, bool want_stats) {
-        // a 1x1 op has no halo: run it over the flattened [B*L] rows as one long sample
-        Act out = new_act(w.n, x.L);
-        const int rows = p->B * x.L;
-        GemmArgs g = gemm_base(out, rows, rows, w);
-        g.B = 1; g.out_rows = rows;
-        g.seg[0] = seg_of(x, nullptr, nullptr, 1.f, 0, 1, 1, 0, 1, w);
-        g.res = res; g.gelu = gelu;
-        run_gemm(g, out, false);
-        (void)want_stats;   // per-sample statistics come from the separate pass (ensure_stats) when needed
-        return out;
-    }
-
-    Act resblock(const std::string& name, Act& x, Act* skip, const ResW& r, int nb) {
-        const int B = p->B, G = h->cfg.resnet_groups;
-        const float sscale = h->cfg.use_skip_scale ? 0.70710678118654752440f : 1.0f;
-        const int ctot = x.C + (skip ? skip->C : 0);
-        if (ctot != r.cin) check("resblock: channel mismatch");
-        double* s0 = ensure_stats(x);
-        double* s1 = skip ? ensure_stats(*skip) : nullptr;
-        static int short_max = -1;       // ADF_SHORT_LEVEL: longest level that materialises silu(GN(x)) for flat GEMM tiles
-        if (short_max < 0) short_max = (int)adf_tuning("ADF_SHORT_LEVEL", 32);
-        const bool short_level = x.L <= short_max && (x.L & (x.L - 1)) == 0;
-        float* ab1 = (float*)alloc((size_t)B * ctot * 2 * 4);
-        GnFinalizeArgs f1;
-        memset(&f1, 0, sizeof(f1));
-        f1.stats0 = s0; f1.stats1 = s1; f1.c0 = x.C; f1.c1 = skip ? skip->C : 0; f1.L = x.L; f1.G = G; f1.B = B;
-        f1.scale1 = sscale; f1.eps = 1e-5f; f1.gamma = r.g1w; f1.beta = r.g1b; f1.film = nullptr; f1.ab = ab1;
-        // short levels in bf16 mode: the whole resblock in one launch (adf_resblock_small.h); ADF_RB_FUSED=0 keeps the separate launches
-        // (2 = four workgroups per sample in two launches when the batch leaves CUs idle, adf_resblock_split.h; 1 = always the one-launch kernel)
-        static int rb_fused = -1;
-        if (rb_fused < 0) rb_fused = adf_route_switch("ADF_RB_FUSED", 2);
-        if (rb_fused && h->bf16 && (x.L == 16 || x.L == 64) && r.cout == 256 && x.C == 256 && (!skip || skip->C == 256) && G == 8 &&
-            r.c1.wfrag && r.c2.wfrag && (!r.has_res || r.cr.wfrag) && r.c1.n_pad == 256 && !(h->cfg.flags & ADF_FLAG_SEPARATE_GN_STATS)) {
-            Act y = new_act(r.cout, x.L);
-            RbFusedArgs fa;
-            memset(&fa, 0, sizeof(fa));
-            fa.x = (const bf16_t*)x.p; fa.skip = skip ? (const bf16_t*)skip->p : nullptr; fa.out = (bf16_t*)y.p;
-            fa.gn1 = f1;
-            fa.gamma2 = r.g2w; fa.beta2 = r.g2b;
-            fa.film = film + r.film_off; fa.film_bstride = nb == 1 ? 0 : h->film_total;
-            if (film2) { fa.film2 = film2 + r.film_off; fa.film2_bstride = film2_bstride; }
-            fa.w1 = r.c1.wfrag; fa.w2 = r.c2.wfrag; fa.wr = r.has_res ? r.cr.wfrag : nullptr;
-            fa.b1 = r.c1.bias; fa.b2 = r.c2.bias; fa.br = r.has_res ? r.cr.bias : nullptr;
-            fa.skip_scale = sscale; fa.eps = 1e-5f;
-            y.stats = alloc_stats(); fa.stats = y.stats;
-            if (rb_fused >= 2 && B * 4 <= 256) {
-                Act hact = new_act(r.cout, x.L);
-                RbSplitArgs sa;
-                sa.f = fa; sa.hact = (bf16_t*)hact.p;
-                if (live()) check(launch_resblock_split(sa, B, x.L, ctot, s));
-            } else if (live()) check(launch_resblock_small(fa, B, x.L, ctot, s));
-            RbRec rec{name, GemmArgs{}, GemmArgs{}, r.cin, r.cout, x.L};
-            rec.g1.nseg = 0;                               // marks a fused block for adf_bench_resblock (keeps the block numbering)
-            p->rbs.push_back(rec);
-            tap(name, y);
-            return y;
-        }
-        Act h1 = new_act(r.cout, x.L);
-        GemmArgs g1 = gemm_base(h1, x.L, x.L, r.c1);
-        if (short_level) {
-            // short levels: one launch normalises + activates the (concatenated) input; the GEMM then takes raw tiles
-            Act a1 = new_act(ctot, x.L);
-            if (live()) check(launch_gn_norm_apply(x.p, skip ? skip->p : nullptr, f1, 1, a1.p, h->bf16, s));
-            g1.seg[0] = seg_of(a1, nullptr, nullptr, 1.f, 0, 3, 1, -1, 1, r.c1);
-        } else {
-            g1.seg[0] = seg_of(x, skip, ab1, sscale, 1, 3, 1, -1, 1, r.c1);
-            g1.seg[0].gn = f1;           // launch_conv_gemm derives the table (in the DMA kernel) or launches gn_finalize
-        }
-        run_gemm(g1, h1, true);
-        tap(name + ".h1", h1);        // the block's stored intermediate (not there when the whole block is one launch)
-        double* sh = ensure_stats(h1);
-        float* ab2 = (float*)alloc((size_t)B * r.cout * 2 * 4);
-        GnFinalizeArgs f2;
-        memset(&f2, 0, sizeof(f2));
-        f2.stats0 = sh; f2.c0 = r.cout; f2.L = x.L; f2.G = G; f2.B = B; f2.scale1 = 1.f; f2.eps = 1e-5f;
-        f2.gamma = r.g2w; f2.beta = r.g2b;
-        f2.film = film + r.film_off; f2.film_bstride = nb == 1 ? 0 : h->film_total; f2.ab = ab2;
-        if (film2) { f2.film2 = film2 + r.film_off; f2.film2_bstride = film2_bstride; }
-        Act y = new_act(r.cout, x.L);
-        GemmArgs g2 = gemm_base(y, x.L, x.L, r.c2);
-        if (short_level) {
-            Act a2 = new_act(r.cout, x.L);
-            if (live()) check(launch_gn_norm_apply(h1.p, nullptr, f2, 1, a2.p, h->bf16, s));
-            g2.seg[0] = seg_of(a2, nullptr, nullptr, 1.f, 0, 3, 1, -1, 1, r.c2);
-        } else {
-            g2.seg[0] = seg_of(h1, nullptr, ab2, 1.f, 1, 3, 1, -1, 1, r.c2);
-            g2.seg[0].gn = f2;
-        }
-        if (r.has_res) {
-            g2.nseg = 2;
-            g2.seg[1] = seg_of(x, skip, nullptr, sscale, 0, 1, 1, 0, 1, r.cr);
-            g2.bias1 = r.cr.bias;
-        } else {
-            if (skip) check("resblock: identity residual with a skip input");
-            g2.res = x.p;
-        }
-        run_gemm(g2, y, true);
-        p->rbs.push_back({name, g1, g2, r.cin, r.cout, x.L});
-        tap(name, y);
-        return y;
-    }
-
-    Act transformer(const std::string& name, Act& x, const TrW& t) {
-        const long long rows = (long long)p->B * x.L;
-        // short levels in bf16 mode: the whole block in one launch (adf_transformer.h); ADF_TR_FUSED=0 keeps the nine launches
-        static int tr_fused = -1;
-        if (tr_fused < 0) tr_fused = adf_route_switch("ADF_TR_FUSED", 2);
-        if (tr_fused && h->bf16 && t.c == 256 && t.mid == 512 && h->cfg.attention_heads == 8 && (x.L == 16 || x.L == 64) &&
-            x.C == 256 && t.qkv.nchunk == 4 && t.ff2.nchunk == 8 && t.qkv.wfrag) {
-            Act x2 = new_act(t.c, x.L);
-            TrFusedArgs fa;
-            memset(&fa, 0, sizeof(fa));
-            fa.x = (const bf16_t*)x.p; fa.out = (bf16_t*)x2.p;
-            fa.ln_w = t.lnw; fa.ln_b = t.lnb; fa.g0 = t.g0; fa.g3 = t.g3;
-            fa.wqkv = t.qkv.wfrag; fa.wproj = t.proj.wfrag; fa.wff1 = t.ff1.wfrag; fa.wff2 = t.ff2.wfrag;
-            fa.npad_qkv = t.qkv.n_pad; fa.npad_proj = t.proj.n_pad; fa.npad_ff1 = t.ff1.n_pad; fa.npad_ff2 = t.ff2.n_pad;
-            fa.eps = 1e-5f;
-            if (h->cfg.resnet_groups == 8 && !(h->cfg.flags & ADF_FLAG_SEPARATE_GN_STATS)) { x2.stats = alloc_stats(); fa.stats = x2.stats; }
-            if (live()) check(launch_transformer_small(fa, p->B, x.L, s));
-            tap(name, x2);
-            return x2;
-        }
-        // longer samples (256 tokens): two fused launches around the attention kernel (ADF_TR_FUSED=1 keeps these unfused)
-        if (tr_fused >= 2 && h->bf16 && t.c == 256 && t.mid == 512 && h->cfg.attention_heads == 8 && x.L % 64 == 0 && x.L > 64 &&
-            x.C == 256 && t.qkv.nchunk == 4 && t.ff2.nchunk == 8 && t.qkv.wfrag && h->cfg.resnet_groups == 8 &&
-            !(h->cfg.flags & ADF_FLAG_SEPARATE_GN_STATS)) {
-            Act qkv = new_act(3 * t.c, x.L), att = new_act(t.c, x.L), x2 = new_act(t.c, x.L);
-            TrFusedArgs fa;
-            memset(&fa, 0, sizeof(fa));
-            fa.x = (const bf16_t*)x.p; fa.out = (bf16_t*)x2.p; fa.qkv_out = (bf16_t*)qkv.p; fa.att = (const bf16_t*)att.p;
-            fa.ln_w = t.lnw; fa.ln_b = t.lnb; fa.g0 = t.g0; fa.g3 = t.g3;
-            fa.wqkv = t.qkv.wfrag; fa.wproj = t.proj.wfrag; fa.wff1 = t.ff1.wfrag; fa.wff2 = t.ff2.wfrag;
-            fa.npad_qkv = t.qkv.n_pad; fa.npad_proj = t.proj.n_pad; fa.npad_ff1 = t.ff1.n_pad; fa.npad_ff2 = t.ff2.n_pad;
-            fa.eps = 1e-5f;
-            x2.stats = alloc_stats(); fa.stats = x2.stats;
-            if (live()) {
-                check(launch_transformer_tiles(fa, (int)rows, x.L, 1, s));
-                check(launch_attention(qkv.p, att.p, h->bf16, p->B, x.L, t.c, h->cfg.attention_heads, s));
-                check(launch_transformer_tiles(fa, (int)rows, x.L, 2, s));
-            }
-            tap(name + ".qkv", qkv);
-            tap(name + ".att", att);
-            tap(name, x2);
-            return x2;
-        }
-        // the nine-launch path: every stored tensor of the block is a recorded activation (the parity tests hold each launch to
-        // the oracle on its own; the fused kernels above are then held to this path)
-        Act xn = new_act(t.c, x.L);
-        if (live()) check(launch_ln_rows(x.p, xn.p, h->bf16, rows, t.c, t.lnw, t.lnb, 1e-5f, s));
-        tap(name + ".ln", xn);
-        Act qkv = linear(xn, t.qkv, nullptr, 0, false);
-        tap(name + ".qkv", qkv);
-        Act att = new_act(t.c, x.L);
-        if (live()) check(h->x3 ? launch_attention_x3(qkv.p, att.p, p->B, x.L, t.c, h->cfg.attention_heads, s)
-                                : launch_attention(qkv.p, att.p, h->bf16, p->B, x.L, t.c, h->cfg.attention_heads, s));
-        tap(name + ".att", att);
-        Act x1 = linear(att, t.proj, x.p, 0, false);
-        tap(name + ".x1", x1);
-        Act n1 = new_act(t.c, x.L);
-        if (live()) check(launch_ln_rows(x1.p, n1.p, h->bf16, rows, t.c, t.g0, nullptr, 1e-5f, s));
-        tap(name + ".n1", n1);
-        Act f1 = linear(n1, t.ff1, nullptr, 1, false);
-        tap(name + ".f1", f1);
-        Act n2 = new_act(t.mid, x.L);
-        if (live()) check(launch_ln_rows(f1.p, n2.p, h->bf16, rows, t.mid, t.g3, nullptr, 1e-5f, s));
-        tap(name + ".n2", n2);
-        Act x2 = linear(n2, t.ff2, x1.p, 0, true);
-        tap(name, x2);
-        return x2;
-    }
 };
 
-struct FwdIO {
-    const float* x = nullptr; float* out = nullptr;
-    const float* t = nullptr; int t_stride = 0; int nb = 0;
-    const float* coef = nullptr; int coef_bstride = 0; const float* x_noisy = nullptr;
-    int mode = 0;                                          // 0: raw network output; 1: clamp(c_skip x_noisy + c_out F, -1, 1); 2: the same unclipped (UNet2dBase only)
-    const float* film2 = nullptr; int film2_bstride = 0;   // class part of the FiLM projections (rows of adf_handle::cond_film)
-    const float* film_pre = nullptr;                       // this evaluation's row of Plan::film_all: sigma embedding + FiLM already computed
-    const float* temb_pre = nullptr;                       // this evaluation's row of Plan::temb_all (class-conditional ADM net: the FiLM rows are per sample)
-    bool null_cond = false;                                // class-conditional ADM net: every sample takes the null class embedding (guidance branch)
-};
-
-int wn_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s);
-int adm_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s);
-int u2d_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s);
-
+// the head of every create call (null arguments, a HIP device exists) and, after its own argument checks, the tail: a handle on the current
+// device with the storage mode of `dtype` that owns `net`, its registry built
+int create_begin(const char* fn, const void* cfg, adf_handle** out);
+int create_finish(const char* fn, int dtype, std::unique_ptr<Net> net, adf_handle** out);
 int forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s);
-int wn_pack_weights(adf_handle* h, hipStream_t s);
-int wn_build_weights(adf_handle* h);
-int adm_build_weights(adf_handle* h);
-int u2d_build_weights(adf_handle* h);
 int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out);
 int cond_rows(adf_handle* h, int B, bool null_branch, FwdIO& io);
 int ensure_cfg_buffers(adf_handle* h, Plan* p);
@@ -676,7 +341,7 @@ struct SamplerCtx {
             FwdIO io;
             io.x = x; io.t = p->coef_all + (size_t)k * 4 + 1; io.t_stride = 4; io.nb = 1;
             io.coef = p->coef_all + (size_t)k * 4; io.coef_bstride = 0; io.x_noisy = x;
-            if ((h->adm || h->u2d) && h->cdim > 0) io.temb_pre = p->temb_all + (size_t)k * 4 * h->cfg.channels;
+            if (h->per_sample_film()) io.temb_pre = p->temb_all + (size_t)k * h->net->dims.temb;
             else io.film_pre = p->film_all + (size_t)k * h->film_total;
             return denoise_io(h, p, io, out, s);
         }

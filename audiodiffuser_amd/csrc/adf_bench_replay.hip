@@ -1,5 +1,6 @@
 // adf_bench_* of include/audiodiffuser_amd.h: HIP-event replays of single launches of the last network pass (bench.py's roofline object).
 #include "adf_api_internal.h"
+#include "adf_net_wavenet.h"
 
 using namespace adf;
 using namespace adf_api;
@@ -46,7 +47,7 @@ static int bench_resblock_impl(adf_handle* h, int B, int L, int level, int conv,
     };
     const size_t rot_min = (size_t)320 << 20;
     auto copies = [&](const GemmArgs& g) { const size_t sb = set_bytes(g); size_t n = (rot_min + sb - 1) / sb; return n < 3 ? (size_t)3 : n; };
-    const size_t stats_bytes = ((size_t)B * h->cfg.resnet_groups * 2 * sizeof(double) + 255) & ~(size_t)255;
+    const size_t stats_bytes = ((size_t)B * h->net->dims.stat_groups * 2 * sizeof(double) + 255) & ~(size_t)255;
     const size_t need = std::max(set_bytes(r.g1) * copies(r.g1), set_bytes(r.g2) * copies(r.g2)) + stats_bytes;
     if (p->bench_cap < need) {
         if (hipStreamSynchronize(s) != hipSuccess) return fail(h, "bench_resblock: stream sync failed");
@@ -115,7 +116,8 @@ int adf_bench_layer(adf_handle* h, int B, int L, int level, int conv, int iters,
 
 int adf_bench_wavenet_layer(adf_handle* h, int B, int T, int layer, int iters, float* ms, double* algo_bytes, double* flops, void* stream) {
     ADF_ON_DEVICE(h);
-    if (!h->wn) return fail(h, "adf_bench_wavenet_layer: not a WaveNetNoise handle");
+    const WavenetNet* wn = dynamic_cast<const WavenetNet*>(h->net.get());
+    if (!wn) return fail(h, "adf_bench_wavenet_layer: not a WaveNetNoise handle");
     hipStream_t s = (hipStream_t)stream;
     Plan* p;
     if (get_plan(h, B, T, s, &p)) return 1;
@@ -133,7 +135,7 @@ int adf_bench_wavenet_layer(adf_handle* h, int B, int T, int layer, int iters, f
     if (!err && hipEventElapsedTime(&t, e0, e1) != hipSuccess) err = "hipEventElapsedTime failed";
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (err) return fail(h, err);
-    const double C = h->wn->cfg.residual_channels, pos = (double)B * T, esz = h->esz;
+    const double C = wn->cfg.residual_channels, pos = (double)B * T, esz = h->esz;
     *ms = t / (float)iters;
     // per position: read y, write y_next (not for the last layer), skip read-modify-write in fp32 (first layer: write only);
     // per launch: both weight matrices once.  Flops: the K = 3C and K = C GEMMs onto 2C columns each.

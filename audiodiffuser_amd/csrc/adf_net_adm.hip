@@ -1,16 +1,52 @@
-// ADM-style UNetModel behind the C ABI (reference: src/models/backbones/unet2d_oai.py:382-635): registry and the block walk.
-#include "adf_api_internal.h"
+// ADM-style UNetModel behind the C ABI (reference: src/models/backbones/unet2d_oai.py:382-635): adf_adm_create, registry and the block walk.
+#include "adf_walk2d.h"
 
 using namespace adf;
 using namespace adf_api;
 
 namespace adf_api {
 
+// ADM-style 2-D U-Net (unet2d_oai.py:382-635): the module list of UNetModel.__init__ as data
+struct AdmRes { int cin = 0, cout = 0, film_off = 0; float *g1w = nullptr, *g1b = nullptr, *g2w = nullptr, *g2b = nullptr; ConvW c1, c2, skip; bool has_skip = false;
+                int updown = 0; };        // 1: ResBlock(up=True), 2: ResBlock(down=True) (resblock_updown, unet2d_oai.py:197-207, :249-254)
+struct AdmAttn { int c = 0, heads = 0; float *gw = nullptr, *gb = nullptr; ConvW qkv, proj; float* qkv_tmp = nullptr; };
+struct AdmLayer { int kind; int idx; };       // kind: 0 input conv, 1 ResBlock, 2 AttentionBlock, 3 Downsample (conv), 4 Upsample (conv), 5 average pool, 6 nearest x 2
+struct AdmNet : Net {
+    adf_adm_config cfg;
+    std::vector<AdmRes> res;
+    std::vector<AdmAttn> attn;
+    std::vector<ConvW> resample;
+    std::vector<std::vector<AdmLayer>> input_blocks, output_blocks;
+    std::vector<AdmLayer> middle;
+    std::vector<int> skip_ch;            // channels of the input-block outputs, in push order
+    float *in_w = nullptr, *in_b = nullptr, *t_w1 = nullptr, *t_b1 = nullptr, *t_w2 = nullptr, *t_b2 = nullptr;
+    float *out_gw = nullptr, *out_gb = nullptr, *out_w = nullptr, *out_b = nullptr;
+    int input_ch = 0, final_ch = 0;
+    int fg = 4;                          // channels per fine statistics group: gcd of every GroupNorm group size of the net (incl. the skip concats)
+
+    AdmNet() { class_in_temb = true; image = true; }
+    int build_weights(adf_handle* h) override;
+    int check_image(adf_handle* h, int L) override;
+    int forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) override;
+    const char* time_embed(const float* t, int t_stride, int n, float* temb, hipStream_t s) override {
+        return launch_adm_time_embed(t, t_stride, n, cfg.model_channels, t_w1, t_b1, t_w2, t_b2, 4 * cfg.model_channels, temb, s);
+    }
+};
+
+int AdmNet::check_image(adf_handle* h, int L) {
+    int f = 1;
+    for (int i = 1; i < cfg.n_mult; ++i) f *= 2;
+    if (H < 1 || W < 1 || (long long)H * W != L) return fail(h, "UNetModel: call adf_set_image_shape(H, W) with H * W equal to the length argument first");
+    if (H % f || W % f || ((H / f) * (W / f)) % 64)
+        return fail(h, "UNetModel: H and W must be multiples of 2^(levels-1) and the coarsest level a multiple of 64 pixels");
+    return 0;
+}
+
 // ---- ADM-style 2-D U-Net ---------------------------------------------------------------------------------------------
 // The module list UNetModel.__init__ builds (unet2d_oai.py:467-594), registered in state_dict order.
-int adm_build_weights(adf_handle* h) {
-    AdmW& a = *h->adm;
-    const adf_adm_config& c = a.cfg;
+int AdmNet::build_weights(adf_handle* h) {
+    AdmNet& a = *this;
+    const adf_adm_config& c = cfg;
     const int mc = c.model_channels, ted = 4 * mc;
     auto has_att = [&](int ds) { for (int i = 0; i < c.n_attention_ds; ++i) if (c.attention_ds[i] == ds) return true; return false; };
     auto heads_of = [&](int ch) { return c.num_head_channels == -1 ? c.num_heads : ch / c.num_head_channels; };
@@ -87,17 +123,8 @@ int adm_build_weights(adf_handle* h) {
     a.t_b1 = R.reg_f32("time_embed.0.bias", ted);
     a.t_w2 = R.reg_f32("time_embed.2.weight", (int64_t)ted * ted);
     a.t_b2 = R.reg_f32("time_embed.2.bias", ted);
-    if (c.num_classes > 0) {             // LabelEmbedder(num_classes, None, model_channels, 4 * model_channels), conditioner.py:64-90; unet2d_oai.py:461-468
-        h->cdim = ted;
-        h->lab_null = R.reg_f32("label_conditioner.null_classes_emb", mc);
-        h->lab_emb = R.reg_f32("label_conditioner.label_emb.weight", (int64_t)c.num_classes * mc);
-        h->lab_lnw = R.reg_f32("label_conditioner.class_to_cond.0.weight", mc);
-        h->lab_lnb = R.reg_f32("label_conditioner.class_to_cond.0.bias", mc);
-        h->lab_w1 = R.reg_f32("label_conditioner.class_to_cond.1.weight", (int64_t)ted * mc);
-        h->lab_b1 = R.reg_f32("label_conditioner.class_to_cond.1.bias", ted);
-        h->lab_w2 = R.reg_f32("label_conditioner.class_to_cond.3.weight", (int64_t)ted * ted);
-        h->lab_b2 = R.reg_f32("label_conditioner.class_to_cond.3.bias", ted);
-    }
+    // LabelEmbedder(num_classes, None, model_channels, 4 * model_channels), conditioner.py:64-90; unet2d_oai.py:461-468
+    if (c.num_classes > 0) R.label_embedder(mc, ted, c.num_classes);
     auto reg_layer = [&](const AdmLayer& l, const std::string& pre) {
         if (l.kind == 0) {
             a.in_w = R.reg_f32(pre + ".weight", (int64_t)a.input_ch * c.in_channels * 9);
@@ -146,85 +173,15 @@ int adm_build_weights(adf_handle* h) {
 }
 
 // UNetModel.forward (unet2d_oai.py:603-634) on channels-last activations; x / out are the reference's [B][C][H][W] fp32
-int adm_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
-    AdmW& a = *h->adm;
-    const adf_adm_config& c = a.cfg;
-    Walker W{h, p, s};
-    p->arena_off = 0; p->stats_off = 0;
-    p->taps.clear(); p->rbs.clear();
-    const int B = p->B, ted = 4 * c.model_channels;
-    if (!p->dry && p->stats_bytes && hipMemsetAsync(p->stats, 0, p->stats_bytes, s) != hipSuccess) return fail(h, "hipMemsetAsync(stats) failed");
-    const float* film = io.film_pre ? io.film_pre : p->film;
-    int film_bs = io.nb > 1 ? h->film_total : 0;
-    if (h->cdim > 0) {
-        // class-conditional: emb[b] = time_embed(t) + label_conditioner(classes[b]) (unet2d_oai.py:619-623), so every sample has its own FiLM rows
-        float* emb_b = (float*)W.alloc((size_t)B * ted * 4);
-        film = p->film; film_bs = h->film_total;
-        if (W.live()) {
-            const float* te = io.temb_pre;
-            int te_bs = 0;
-            if (!te) {
-                W.check(launch_adm_time_embed(io.t, io.t_stride, io.nb, c.model_channels, a.t_w1, a.t_b1, a.t_w2, a.t_b2, ted, p->temb, s));
-                te = p->temb; te_bs = io.nb > 1 ? ted : 0;
-            }
-            const float* ce = io.null_cond ? h->cond_emb + (size_t)B * ted : h->cond_emb;       // last row = the null embedding
-            W.check(launch_add_rows(emb_b, te, te_bs, ce, io.null_cond ? 0 : ted, B, ted, s));
-            W.check(launch_film(emb_b, ted, h->film_w, ted, 0, h->film_b, p->film, B, h->film_total, s));
-        }
-    } else if (W.live() && !io.film_pre) {
-        W.check(launch_adm_time_embed(io.t, io.t_stride, io.nb, c.model_channels, a.t_w1, a.t_b1, a.t_w2, a.t_b2, ted, p->temb, s));
-        W.check(launch_film(p->temb, ted, h->film_w, ted, 0, h->film_b, p->film, io.nb, h->film_total, s));
-    }
-    // st: FINE GroupNorm statistics of the tensor ([B][C / fg][2]), when its producer reduced them; t1 / st1: the second source of a virtual
-    // concat (the skip of an output block, unet2d_oai.py:629: never materialised -- convs and the GroupNorm table read both sources)
-    struct T2 { Act t; int H, W; double* st = nullptr; Act t1; double* st1 = nullptr; };
-    const int fg = a.fg;
-    auto alloc_fine = [&](int C) -> double* {
-        const size_t bytes = ((size_t)B * (C / fg) * 2 * sizeof(double) + 255) & ~(size_t)255;
-        const size_t off = p->stats_off;
-        p->stats_off += bytes;
-        if (p->dry) return (double*)(uintptr_t)(off + 256);
-        if (p->stats_off > p->stats_bytes) { W.check("stats arena overflow"); return nullptr; }
-        return (double*)(p->stats + off);
-    };
-    auto ensure_stats = [&](const Act& t, double*& st) {
-        if (st) return;
-        st = alloc_fine(t.C);
-        if (W.live()) W.check(launch_gn_stats_any(t.p, h->bf16, B, t.L, t.C, t.C / fg, st, s));
-    };
-    // GroupNorm32 (:10-21) (+ scale-shift, :262-267) of a tensor (or a virtual concat) folded to the per-(sample, channel) table a conv prologue reads
-    auto gn_table = [&](T2& x, const float* gamma, const float* beta, const float* fl) -> float* {
-        ensure_stats(x.t, x.st);
-        if (x.t1.p || x.t1.C) ensure_stats(x.t1, x.st1);
-        const int ctot = x.t.C + x.t1.C;
-        float* ab = (float*)W.alloc((size_t)B * ctot * 2 * 4);
-        if (W.live()) {
-            GnFineArgs g;
-            memset(&g, 0, sizeof(g));
-            g.stats0 = x.st; g.stats1 = x.st1; g.c0 = x.t.C; g.c1 = x.t1.C; g.L = x.t.L; g.G = 32; g.B = B; g.fg = fg; g.eps = 1e-5f;
-            g.gamma = gamma; g.beta = beta; g.film = fl; g.film_bstride = film_bs; g.ab = ab;
-            W.check(launch_gn_finalize_fine(g, s));
-        }
-        return ab;
-    };
-    // stats: also reduce the (fine) GroupNorm statistics of the output in the epilogue (where a GroupNorm reads this tensor next)
-    auto conv = [&](const T2& x, const ConvW& w, const float* ab, int act, int mode, const void* res, bool stats, const float* bias_b = nullptr) -> T2 {
-        T2 y;
-        if (stats && w.cout % fg == 0 && (w.cout <= 128 || w.cout % 128 == 0)) y.st = alloc_fine(w.cout);
-        y.H = mode == 1 ? x.H * 2 : (mode == 2 ? x.H / 2 : x.H);
-        y.W = mode == 1 ? x.W * 2 : (mode == 2 ? x.W / 2 : x.W);
-        y.t = W.new_act(w.cout, y.H * y.W);
-        if (W.live()) {
-            Conv2dArgs g;
-            g.x = x.t.p; g.x1 = x.t1.C ? x.t1.p : nullptr; g.c0 = x.t.C;
-            g.ab = ab; g.act = act; g.B = B; g.H = y.H; g.W = y.W; g.cin = x.t.C + x.t1.C; g.cout = w.cout; g.n_pad = w.n_pad;
-            g.taps = w.taps; g.mode = mode; g.w = w.w; g.nchunk = w.nchunk; g.bias = w.bias; g.res = res; g.out = y.t.p;
-            g.bias_b = bias_b; g.bias_bstride = film_bs;
-            g.stats = y.st; g.stats_groups = w.cout / fg;
-            W.check(launch_conv2d(g, h->bf16, s));
-        }
-        return y;
-    };
+int AdmNet::forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
+    AdmNet& a = *this;
+    const adf_adm_config& c = cfg;
+    // GroupNorm32 (:10-21); no skip scale; every conv on the MFMA route; additive conditioning as a per-sample bias
+    Walk2d W{{h, p, s}, 32, fg, 1.0f, false, true};
+    if (W.begin()) return 1;
+    W.condition(io);
+    const int B = p->B;
+    const float* const film = W.film;
     auto run = [&](const std::vector<AdmLayer>& ls, T2 x, const std::string& bname) -> T2 {
         int lj = -1;
         for (const AdmLayer& l : ls) {
@@ -233,13 +190,13 @@ int adm_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
             if (W.bad) break;
             if (l.kind == 0) {
                 T2 y; y.H = x.H; y.W = x.W; y.t = W.new_act(a.input_ch, x.H * x.W);
-                y.st = alloc_fine(a.input_ch);   // here, so that the copy pushed on the skip stack carries them (the last output block reads them again)
+                y.st = W.alloc_fine(a.input_ch);   // here, so that the copy pushed on the skip stack carries them (the last output block reads them again)
                 if (W.live()) W.check(launch_conv2d_in(io.x, a.in_w, a.in_b, y.t.p, h->bf16, B, c.in_channels, x.H, x.W, a.input_ch, io.coef, io.coef_bstride, y.st, fg, s));
                 x = y;
                 W.tap(ln, x.t);
             } else if (l.kind == 1) {                                  // ResBlock._forward, :248-272
                 const AdmRes& r = a.res[l.idx];
-                const float* ab1 = gn_table(x, r.g1w, r.g1b, nullptr);
+                const float* ab1 = W.gn_table(x, r.g1w, r.g1b, nullptr);
                 // scale-shift form (:262-267): the embedding enters the out_norm table; additive form (:268-270, h = out_norm(h + emb_out)): it is a
                 // per-sample addend to conv1's bias, so that the stored tensor (and the statistics reduced from it) is h + emb_out
                 const bool ss = c.use_scale_shift_norm != 0;
@@ -255,35 +212,35 @@ int adm_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
                         W.check(launch_avgpool2(x.t.p, ab1, 1, p1.t.p, h->bf16, B, x.H, x.W, r.cin, s));
                         W.check(launch_avgpool2(x.t.p, nullptr, 0, p2.t.p, h->bf16, B, x.H, x.W, r.cin, s));
                     }
-                    hh = conv(p1, r.c1, nullptr, 0, 0, nullptr, true, emb_b);
+                    hh = W.conv(p1, r.c1, nullptr, 0, 0, nullptr, true, emb_b);
                     x = p2;
                 } else if (r.updown == 1) {
                     // ResBlock(up=True): h = in_conv(nearest x 2 (in_rest(x))) -- the upsampling is an index map of the conv's gather (mode 1),
                     // x = nearest x 2 (x) is written once (it is the block's residual)
                     if (x.t1.C) { W.check("ResBlock(up=True) on a skip concat"); break; }
-                    hh = conv(x, r.c1, ab1, 1, 1, nullptr, true, emb_b);
+                    hh = W.conv(x, r.c1, ab1, 1, 1, nullptr, true, emb_b);
                     T2 u2; u2.H = x.H * 2; u2.W = x.W * 2; u2.t = W.new_act(r.cin, u2.H * u2.W);
                     if (W.live()) W.check(launch_nearest_up2(x.t.p, u2.t.p, h->bf16, B, x.H, x.W, r.cin, s));
                     x = u2;
-                } else hh = conv(x, r.c1, ab1, 1, 0, nullptr, true, emb_b);
+                } else hh = W.conv(x, r.c1, ab1, 1, 0, nullptr, true, emb_b);
                 W.tap(ln + ".h1", hh.t);
-                const float* ab2 = gn_table(hh, r.g2w, r.g2b, ss ? film + r.film_off : nullptr);
+                const float* ab2 = W.gn_table(hh, r.g2w, r.g2b, ss ? film + r.film_off : nullptr);
                 const void* skip = x.t.p;
-                if (r.has_skip) { T2 sk2 = conv(x, r.skip, nullptr, 0, 0, nullptr, false); W.tap(ln + ".skip", sk2.t); skip = sk2.t.p; }
-                x = conv(hh, r.c2, ab2, 1, 0, skip, true);
+                if (r.has_skip) { T2 sk2 = W.conv(x, r.skip, nullptr, 0, 0, nullptr, false); W.tap(ln + ".skip", sk2.t); skip = sk2.t.p; }
+                x = W.conv(hh, r.c2, ab2, 1, 0, skip, true);
                 W.tap(ln, x.t);
             } else if (l.kind == 2) {                                   // AttentionBlock._forward, :316-322
                 const AdmAttn& t = a.attn[l.idx];
-                const float* ab = gn_table(x, t.gw, t.gb, nullptr);
+                const float* ab = W.gn_table(x, t.gw, t.gb, nullptr);
                 T2 xn; xn.H = x.H; xn.W = x.W; xn.t = W.new_act(t.c, x.t.L);
                 if (W.live()) W.check(launch_gn_apply(x.t.p, nullptr, t.c, 0, x.t.L, B, ab, 0, xn.t.p, h->bf16, s));
                 W.tap(ln + ".xn", xn.t);
-                T2 qkv = conv(xn, t.qkv, nullptr, 0, 0, nullptr, false);
+                T2 qkv = W.conv(xn, t.qkv, nullptr, 0, 0, nullptr, false);
                 W.tap(ln + ".qkv", qkv.t);         // q | k | v blocks (the rows were permuted at load for the legacy order)
                 T2 att; att.H = x.H; att.W = x.W; att.t = W.new_act(t.c, x.t.L);
                 if (W.live()) W.check(launch_attention(qkv.t.p, att.t.p, h->bf16, B, x.t.L, t.c, t.heads, s));
                 W.tap(ln + ".att", att.t);
-                x = conv(att, t.proj, nullptr, 0, 0, xn.t.p, true);    // the residual is the NORMALISED input (:318-322)
+                x = W.conv(att, t.proj, nullptr, 0, 0, xn.t.p, true);    // the residual is the NORMALISED input (:318-322)
                 W.tap(ln, x.t);
             } else if (l.kind == 5 || l.kind == 6) {                     // Downsample / Upsample without a conv (conv_resample=False, :122-125, :153-156)
                 if (x.t1.C) { W.check("pooled resampling on a skip concat"); break; }
@@ -294,13 +251,13 @@ int adm_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
                 x = y;
                 W.tap(ln, x.t);
             } else {
-                x = conv(x, a.resample[l.idx], nullptr, 0, l.kind == 3 ? 2 : 1, nullptr, true);
+                x = W.conv(x, a.resample[l.idx], nullptr, 0, l.kind == 3 ? 2 : 1, nullptr, true);
                 W.tap(ln, x.t);
             }
         }
         return x;
     };
-    T2 x; x.H = a.H; x.W = a.W; x.t = Act{};
+    T2 x; x.H = H; x.W = this->W; x.t = Act{};
     std::vector<T2> hs;
     for (size_t i = 0; i < a.input_blocks.size() && !W.bad; ++i) {
         x = run(a.input_blocks[i], x, "input_blocks." + std::to_string(i));
@@ -317,7 +274,7 @@ int adm_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
         x = run(a.output_blocks[i], cat, "output_blocks." + std::to_string(i));
         W.tap("output_blocks." + std::to_string(i), x.t);
     }
-    const float* abo = gn_table(x, a.out_gw, a.out_gb, nullptr);
+    const float* abo = W.gn_table(x, a.out_gw, a.out_gb, nullptr);
     if (W.live())
         W.check(launch_conv2d_out(x.t.p, abo, a.out_w, a.out_b, io.out, h->bf16, B, a.final_ch, x.H, x.W, c.out_channels, io.mode, io.x_noisy, io.coef,
                                   io.coef_bstride, s));
@@ -325,3 +282,21 @@ int adm_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
 }
 
 }  // namespace adf_api
+
+extern "C" int adf_adm_create(const adf_adm_config* cfg, adf_handle** out) {
+    if (create_begin("adf_adm_create", cfg, out)) return 1;
+    const adf_adm_config& c = *cfg;
+    const int kc = c.dtype == ADF_DTYPE_BF16 ? 64 : 32;
+    if (c.dtype != ADF_DTYPE_F32 && c.dtype != ADF_DTYPE_BF16) { g_create_error = "adf_adm_create: bad dtype"; return 1; }
+    if (c.n_mult < 1 || c.n_mult > ADF_ADM_MAX_LEVELS || c.num_res_blocks < 1 || c.n_attention_ds < 0 || c.n_attention_ds > ADF_ADM_MAX_LEVELS) { g_create_error = "adf_adm_create: bad level / block counts"; return 1; }
+    if (c.model_channels < 32 || c.model_channels % 32 || c.model_channels % kc || c.model_channels > 256) { g_create_error = "adf_adm_create: model_channels must be a multiple of 32 (fp32) / 64 (bf16), at most 256"; return 1; }
+    if (c.in_channels < 1 || c.out_channels < 1 || c.out_channels > 4) { g_create_error = "adf_adm_create: in_channels >= 1, 1 <= out_channels <= 4"; return 1; }
+    if (c.num_classes < 0) { g_create_error = "adf_adm_create: num_classes must be >= 0"; return 1; }
+    for (int i = 0; i < c.n_mult; ++i) if (c.channel_mult[i] < 1) { g_create_error = "adf_adm_create: bad channel_mult"; return 1; }
+    auto net = std::make_unique<AdmNet>();
+    net->cfg = c;
+    NetDims& d = net->dims;
+    d.in_channels = c.in_channels; d.out_channels = c.out_channels;
+    d.temb = 4 * c.model_channels; d.label_in = c.model_channels; d.num_classes = c.num_classes; d.stat_groups = 32;
+    return create_finish("adf_adm_create", c.dtype, std::move(net), out);
+}

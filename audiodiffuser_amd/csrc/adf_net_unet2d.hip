@@ -1,17 +1,63 @@
-// Imagen-style UNet2dBase behind the C ABI (reference: src/models/backbones/unet2d.py:622-972), exact fp32: registry and the block walk.
+// Imagen-style UNet2dBase behind the C ABI (reference: src/models/backbones/unet2d.py:622-972), exact fp32: adf_unet2d_create, registry and the block walk.
 // The convs and linears go through launch_conv2d (launch_u2d_conv_small below 64 pixels per image), GroupNorm tables through
 // launch_gn_finalize_fine; the layers the ADM net has no kernel for are in adf_unet2d.hip.
-#include "adf_api_internal.h"
+#include "adf_walk2d.h"
 
 using namespace adf;
 using namespace adf_api;
 
 namespace adf_api {
 
+// Imagen-style UNet2dBase (unet2d.py:622-972): the module tree of the memory-efficient layout as data
+struct U2dRes {
+    int cin = 0, cout = 0, skip_c = 0, film_off = 0;   // skip_c: channels of the (scaled) skip half of the input (up blocks), 0 otherwise
+    float *g1w = nullptr, *g1b = nullptr, *g2w = nullptr, *g2b = nullptr;
+    ConvW c1, c2, res;
+    bool has_res = false, gca = false;
+    int gca_hid = 0;
+    float *gk_w = nullptr, *gk_b = nullptr, *gn0_w = nullptr, *gn0_b = nullptr, *gn2_w = nullptr, *gn2_b = nullptr;
+};
+struct U2dTrLayer { ConvW qkv, out, ff1, ff2; float *g0 = nullptr, *g3 = nullptr; };
+struct U2dTr { int c = 0, hid = 0, heads = 0; std::vector<U2dTrLayer> layers; float* norm_g = nullptr; };
+struct U2dLevel {
+    int din = 0, dout = 0;
+    ConvW down;                          // Downsample's 1x1 conv over unshuffled channels, packed as a 3x3 / stride-2 conv (slot kind 6)
+    std::vector<U2dRes> down_rb, up_rb;  // [0] = the block without a gate (ds_block.1 / us_block.0), then the gated ones
+    bool attn = false;
+    U2dTr down_tr, up_tr;
+    ConvW up;                            // PixelShuffleUpsample's 1x1 conv dout -> 4 din
+};
+struct Unet2dNet : Net {
+    adf_unet2d_config cfg;
+    int init_dim = 0, tcd = 0, fg = 4;
+    int ce_off[5] = {0};
+    float *ce_w[4] = {nullptr}, *ce_b[4] = {nullptr};
+    float *fourier = nullptr, *t_w1 = nullptr, *t_b1 = nullptr, *t_w2 = nullptr, *t_b2 = nullptr;
+    U2dRes init_rb, mid1, mid2, final_rb;
+    U2dTr mid_tr;
+    std::vector<U2dLevel> lv;
+    float *out_w = nullptr, *out_b = nullptr;
+
+    Unet2dNet() { class_in_temb = true; unclipped_epilogue = true; image = true; }
+    int build_weights(adf_handle* h) override;
+    int check_image(adf_handle* h, int L) override;
+    int forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) override;
+    const char* time_embed(const float* t, int t_stride, int n, float* temb, hipStream_t s) override {
+        return launch_u2d_time_embed(t, t_stride, n, fourier, cfg.learned_sinu_pos_emb_dim / 2, t_w1, t_b1, t_w2, t_b2, tcd, temb, s);
+    }
+};
+
+int Unet2dNet::check_image(adf_handle* h, int L) {
+    const int f = 1 << cfg.n_levels;
+    if (H < 1 || W < 1 || (long long)H * W != L) return fail(h, "UNet2dBase: call adf_set_image_shape(H, W) with H * W equal to the length argument first");
+    if (H % f || W % f) return fail(h, "UNet2dBase: H and W must be multiples of 2^levels");
+    return 0;
+}
+
 // ---- registry: the registration order of UNet2dBase.__init__ (:679-876) ------------------------------------------------------------
-int u2d_build_weights(adf_handle* h) {
-    U2dW& u = *h->u2d;
-    const adf_unet2d_config& c = u.cfg;
+int Unet2dNet::build_weights(adf_handle* h) {
+    Unet2dNet& u = *this;
+    const adf_unet2d_config& c = cfg;
     const int n = c.n_levels, tcd = u.tcd, cd = c.cond_dim;
     std::vector<int> dims{u.init_dim};
     for (int i = 0; i < n; ++i) dims.push_back(c.dim * c.dim_mults[i]);
@@ -75,18 +121,7 @@ int u2d_build_weights(adf_handle* h) {
     u.t_b2 = R.reg_f32("to_time_cond.0.bias", tcd);
     unused("to_time_tokens.0.weight", (int64_t)cd * c.num_time_tokens * tcd);
     unused("to_time_tokens.0.bias", (int64_t)cd * c.num_time_tokens);
-    if (c.num_classes > 0) {             // LabelEmbedder(num_classes, dim, 4 dim) (:717-727, conditioner.py:65-90)
-        const int cdm = 4 * c.dim;
-        h->cdim = cdm;
-        h->lab_null = R.reg_f32("label_conditioner.null_classes_emb", c.dim);
-        h->lab_emb = R.reg_f32("label_conditioner.label_emb.weight", (int64_t)c.num_classes * c.dim);
-        h->lab_lnw = R.reg_f32("label_conditioner.class_to_cond.0.weight", c.dim);
-        h->lab_lnb = R.reg_f32("label_conditioner.class_to_cond.0.bias", c.dim);
-        h->lab_w1 = R.reg_f32("label_conditioner.class_to_cond.1.weight", (int64_t)cdm * c.dim);
-        h->lab_b1 = R.reg_f32("label_conditioner.class_to_cond.1.bias", cdm);
-        h->lab_w2 = R.reg_f32("label_conditioner.class_to_cond.3.weight", (int64_t)cdm * cdm);
-        h->lab_b2 = R.reg_f32("label_conditioner.class_to_cond.3.bias", cdm);
-    }
+    if (c.num_classes > 0) R.label_embedder(c.dim, 4 * c.dim, c.num_classes);      // LabelEmbedder(num_classes, dim, 4 dim) (:717-727, conditioner.py:65-90)
     // ResnetBlock.__init__ :106-144: time_mlp, cross_attn, block1, block2, gca, res_conv
     auto reg_rb = [&](const std::string& pre, U2dRes& r, bool cross) {
         R.reg_f32(pre + ".time_mlp.1.weight", (int64_t)2 * r.cout * tcd, h->film_w + (size_t)r.film_off * tcd);
@@ -177,111 +212,40 @@ int u2d_build_weights(adf_handle* h) {
 }
 
 // ---- UNet2dBase.forward (:879-972) for text_embeds = None, inj_channels = None, on channels-last fp32 activations --------------------
-int u2d_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
-    U2dW& u = *h->u2d;
-    const adf_unet2d_config& c = u.cfg;
-    Walker W{h, p, s};
-    p->arena_off = 0; p->stats_off = 0;
-    p->taps.clear(); p->rbs.clear();
-    const int B = p->B, tcd = u.tcd, G = c.resnet_groups, fg = u.fg;
-    if (!p->dry && p->stats_bytes && hipMemsetAsync(p->stats, 0, p->stats_bytes, s) != hipSuccess) return fail(h, "hipMemsetAsync(stats) failed");
+int Unet2dNet::forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
+    Unet2dNet& u = *this;
+    const adf_unet2d_config& c = cfg;
+    // the 2^-1/2 of the skip half of cat(x, skip * s) (:530-535) enters the GroupNorm table; images below 64 pixels take the small conv route
+    Walk2d W{{h, p, s}, c.resnet_groups, fg, c.scale_skip_connection ? 0.70710678118654752440f : 1.0f, true, false};
+    if (W.begin()) return 1;
     // conditioning (:898-908): t = to_time_cond(to_time_hiddens(c_noise)) (+ the label embedding), then every block's time_mlp (SiLU -> Linear)
-    const float* film = io.film_pre ? io.film_pre : p->film;
-    int film_bs = io.nb > 1 ? h->film_total : 0;
-    if (h->cdim > 0) {
-        float* emb_b = (float*)W.alloc((size_t)B * tcd * 4);
-        film = p->film; film_bs = h->film_total;
-        if (W.live()) {
-            const float* te = io.temb_pre;
-            int te_bs = 0;
-            if (!te) {
-                W.check(launch_u2d_time_embed(io.t, io.t_stride, io.nb, u.fourier, c.learned_sinu_pos_emb_dim / 2, u.t_w1, u.t_b1, u.t_w2, u.t_b2, tcd,
-                                              p->temb, s));
-                te = p->temb; te_bs = io.nb > 1 ? tcd : 0;
-            }
-            const float* ce = io.null_cond ? h->cond_emb + (size_t)B * tcd : h->cond_emb;       // last row = the null embedding
-            W.check(launch_add_rows(emb_b, te, te_bs, ce, io.null_cond ? 0 : tcd, B, tcd, s));
-            W.check(launch_film(emb_b, tcd, h->film_w, tcd, 0, h->film_b, p->film, B, h->film_total, s));
-        }
-    } else if (W.live() && !io.film_pre) {
-        W.check(launch_u2d_time_embed(io.t, io.t_stride, io.nb, u.fourier, c.learned_sinu_pos_emb_dim / 2, u.t_w1, u.t_b1, u.t_w2, u.t_b2, tcd,
-                                      p->temb, s));
-        W.check(launch_film(p->temb, tcd, h->film_w, tcd, 0, h->film_b, p->film, io.nb, h->film_total, s));
-    }
-    // st: FINE GroupNorm statistics ([B][C / fg][2]) when the producer reduced them; t1 / st1: the skip half of a virtual concat (never materialised)
-    struct T2 { Act t; int H = 0, W = 0; double* st = nullptr; Act t1; double* st1 = nullptr; };
-    auto alloc_fine = [&](int C) -> double* {
-        const size_t bytes = ((size_t)B * (C / fg) * 2 * sizeof(double) + 255) & ~(size_t)255;
-        const size_t off = p->stats_off;
-        p->stats_off += bytes;
-        if (p->dry) return (double*)(uintptr_t)(off + 256);
-        if (p->stats_off > p->stats_bytes) { W.check("stats arena overflow"); return nullptr; }
-        return (double*)(p->stats + off);
-    };
-    auto ensure_stats = [&](const Act& t, double*& st) {
-        if (st) return;
-        st = alloc_fine(t.C);
-        if (W.live()) W.check(launch_gn_stats_any(t.p, 0, B, t.L, t.C, t.C / fg, st, s));
-    };
-    const float skip_scale = c.scale_skip_connection ? 0.70710678118654752440f : 1.0f;
-    // Block's GroupNorm (+ time scale-shift, :96-104) folded to the per-(sample, channel) table of the conv prologue
-    auto gn_table = [&](T2& x, const float* gamma, const float* beta, const float* fl) -> float* {
-        ensure_stats(x.t, x.st);
-        if (x.t1.C) ensure_stats(x.t1, x.st1);
-        const int ctot = x.t.C + x.t1.C;
-        float* ab = (float*)W.alloc((size_t)B * ctot * 2 * 4);
-        if (W.live()) {
-            GnFineArgs g;
-            memset(&g, 0, sizeof(g));
-            g.stats0 = x.st; g.stats1 = x.st1; g.c0 = x.t.C; g.c1 = x.t1.C; g.L = x.t.L; g.G = G; g.B = B; g.fg = fg; g.eps = 1e-5f;
-            g.gamma = gamma; g.beta = beta; g.film = fl; g.film_bstride = film_bs; g.ab = ab;
-            W.check(x.t1.C && skip_scale != 1.0f ? launch_u2d_gn_finalize_scaled(g, skip_scale, s) : launch_gn_finalize_fine(g, s));
-        }
-        return ab;
-    };
-    // 3x3 / 1x1 conv or linear; `stats`: also the fine statistics of the output (the MFMA conv's epilogue; a separate pass on small images)
-    auto conv = [&](const T2& x, const ConvW& w, const float* ab, int act, int mode, const void* res, bool stats) -> T2 {
-        T2 y;
-        y.H = mode == 2 ? x.H / 2 : x.H;
-        y.W = mode == 2 ? x.W / 2 : x.W;
-        y.t = W.new_act(w.cout, y.H * y.W);
-        const bool tiled = (y.H * y.W) % 64 == 0;
-        if (stats && tiled && w.cout % fg == 0 && (w.cout <= 128 || w.cout % 128 == 0)) y.st = alloc_fine(w.cout);
-        if (W.live()) {
-            Conv2dArgs g;
-            memset(&g, 0, sizeof(g));
-            g.x = x.t.p; g.x1 = x.t1.C ? x.t1.p : nullptr; g.c0 = x.t.C;
-            g.ab = ab; g.act = act; g.B = B; g.H = y.H; g.W = y.W; g.cin = x.t.C + x.t1.C; g.cout = w.cout; g.n_pad = w.n_pad;
-            g.taps = w.taps; g.mode = mode; g.w = w.w; g.nchunk = w.nchunk; g.bias = w.bias; g.res = res; g.out = y.t.p;
-            g.stats = y.st; g.stats_groups = w.cout / fg;
-            W.check(tiled ? launch_conv2d(g, 0, s) : launch_u2d_conv_small(g, s));
-        }
-        return y;
-    };
+    W.condition(io);
+    const int B = p->B;
+    const float* const film = W.film;
     // ResnetBlock.forward :147-168 (cond = None): block1, block2 with the time scale-shift, gca gate, residual
     auto resblock = [&](T2 x, const U2dRes& r, const std::string& name) -> T2 {
         if (x.t.C + x.t1.C != r.cin) { W.check("UNet2dBase: resnet block input width mismatch"); return x; }
-        const float* ab1 = gn_table(x, r.g1w, r.g1b, nullptr);
-        T2 h1 = conv(x, r.c1, ab1, 1, 0, nullptr, true);
+        const float* ab1 = W.gn_table(x, r.g1w, r.g1b, nullptr);
+        T2 h1 = W.conv(x, r.c1, ab1, 1, 0, nullptr, true);
         W.tap(name + ".h1", h1.t);
-        const float* ab2 = gn_table(h1, r.g2w, r.g2b, film + r.film_off);
+        const float* ab2 = W.gn_table(h1, r.g2w, r.g2b, film + r.film_off);
         const void* res = x.t.p;
         if (r.has_res) {
-            T2 rr = conv(x, r.res, nullptr, 0, 0, nullptr, false);      // skip scale folded into its weight columns
+            T2 rr = W.conv(x, r.res, nullptr, 0, 0, nullptr, false);      // skip scale folded into its weight columns
             W.tap(name + ".res", rr.t);
             res = rr.t.p;
         } else if (x.t1.C) { W.check("UNet2dBase: identity residual over a concat"); return x; }
         if (!r.gca) {
-            T2 y = conv(h1, r.c2, ab2, 1, 0, res, true);
+            T2 y = W.conv(h1, r.c2, ab2, 1, 0, res, true);
             W.tap(name, y.t);
             return y;
         }
-        T2 h2 = conv(h1, r.c2, ab2, 1, 0, nullptr, false);
+        T2 h2 = W.conv(h1, r.c2, ab2, 1, 0, nullptr, false);
         W.tap(name + ".h2", h2.t);
         const int L = h2.t.L, C = r.cout;
         float* part = (float*)W.alloc((size_t)B * u2d_gca_chunks(L) * (C + 2) * 4);
         float* gate = (float*)W.alloc((size_t)B * C * 4);
-        T2 y; y.H = h2.H; y.W = h2.W; y.t = W.new_act(C, L); y.st = alloc_fine(C);
+        T2 y; y.H = h2.H; y.W = h2.W; y.t = W.new_act(C, L); y.st = W.alloc_fine(C);
         if (W.live()) {
             W.check(launch_u2d_gca_pool((const float*)h2.t.p, r.gk_w, r.gk_b, B, L, C, part, s));
             W.check(launch_u2d_gca_gate(part, B, L, C, r.gca_hid, r.gn0_w, r.gn0_b, r.gn2_w, r.gn2_b, gate, s));
@@ -299,35 +263,35 @@ int u2d_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
             const bool last = d + 1 == t.layers.size();
             T2 xn = x; xn.st = nullptr; xn.t = W.new_act(t.c, x.t.L);
             if (W.live()) W.check(launch_ln_rows(x.t.p, xn.t.p, 0, rows, t.c, t.norm_g, nullptr, 1e-5f, s));
-            T2 qkv = conv(xn, Ly.qkv, nullptr, 0, 0, nullptr, false);
+            T2 qkv = W.conv(xn, Ly.qkv, nullptr, 0, 0, nullptr, false);
             W.tap(ln + ".qkv", qkv.t);
             T2 att = xn; att.t = W.new_act(t.c, x.t.L);
             if (W.live())
                 W.check(t.c / t.heads == 128 ? launch_u2d_attention_d128((const float*)qkv.t.p, (float*)att.t.p, B, x.t.L, t.c, t.heads, s)
                                              : launch_attention(qkv.t.p, att.t.p, 0, B, x.t.L, t.c, t.heads, s));
             W.tap(ln + ".att", att.t);
-            T2 x1 = conv(att, Ly.out, nullptr, 0, 0, x.t.p, false);
+            T2 x1 = W.conv(att, Ly.out, nullptr, 0, 0, x.t.p, false);
             W.tap(ln + ".x1", x1.t);
             T2 n1 = x1; n1.t = W.new_act(t.c, x.t.L);
             if (W.live()) W.check(launch_ln_rows(x1.t.p, n1.t.p, 0, rows, t.c, Ly.g0, nullptr, 1e-5f, s));
-            T2 f1 = conv(n1, Ly.ff1, nullptr, 0, 0, nullptr, false);
+            T2 f1 = W.conv(n1, Ly.ff1, nullptr, 0, 0, nullptr, false);
             T2 n2 = f1; n2.t = W.new_act(t.hid, x.t.L);
             if (W.live()) W.check(launch_u2d_gelu_ln_rows((const float*)f1.t.p, (float*)n2.t.p, rows, t.hid, Ly.g3, 1e-5f, s));
-            x = conv(n2, Ly.ff2, nullptr, 0, 0, x1.t.p, last);
+            x = W.conv(n2, Ly.ff2, nullptr, 0, 0, x1.t.p, last);
             W.tap(ln, x.t);
         }
         W.tap(name, x.t);
         return x;
     };
     // :890-892 initial convolution: CrossEmbedLayer with c_in fused, and the fine statistics init_resnet_block.block1 reads
-    T2 x; x.H = u.H; x.W = u.W;
-    x.t = W.new_act(u.init_dim, u.H * u.W);
-    x.st = alloc_fine(u.init_dim);
+    T2 x; x.H = H; x.W = this->W;
+    x.t = W.new_act(u.init_dim, H * this->W);
+    x.st = W.alloc_fine(u.init_dim);
     if (W.live()) {
         U2dCrossEmbedArgs ce;
         memset(&ce, 0, sizeof(ce));
         ce.x = io.x; ce.coef = io.coef; ce.coef_bstride = io.coef_bstride;
-        ce.B = B; ce.cin = c.channels; ce.H = u.H; ce.W = u.W; ce.n = c.n_init_kernels;
+        ce.B = B; ce.cin = c.channels; ce.H = H; ce.W = this->W; ce.n = c.n_init_kernels;
         for (int i = 0; i < c.n_init_kernels; ++i) { ce.ks[i] = c.init_kernel_sizes[i]; ce.w[i] = u.ce_w[i]; ce.bias[i] = u.ce_b[i]; }
         for (int i = 0; i <= c.n_init_kernels; ++i) ce.off[i] = u.ce_off[i];
         ce.out = (float*)x.t.p; ce.stats = x.st; ce.fg = fg;
@@ -341,7 +305,7 @@ int u2d_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
     for (int i = 0; i < n && !W.bad; ++i) {
         const U2dLevel& L = u.lv[i];
         const std::string pre = "downs." + std::to_string(i);
-        x = conv(x, L.down, nullptr, 0, 2, nullptr, true);
+        x = W.conv(x, L.down, nullptr, 0, 2, nullptr, true);
         W.tap(pre + ".down", x.t);
         x = resblock(x, L.down_rb[0], pre + ".1");
         for (int j = 0; j < c.num_resnet_blocks; ++j) {
@@ -370,7 +334,7 @@ int u2d_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
         }
         if (L.attn) x = transformer(x, L.up_tr, pre + ".2");
         // PixelShuffleUpsample: 1x1 conv to 4 din, SiLU, pixel shuffle (statistics by the separate pass when the next GroupNorm asks)
-        T2 pre_shuffle = conv(x, L.up, nullptr, 0, 0, nullptr, false);
+        T2 pre_shuffle = W.conv(x, L.up, nullptr, 0, 0, nullptr, false);
         W.tap(pre + ".3.conv", pre_shuffle.t);
         T2 y; y.H = 2 * x.H; y.W = 2 * x.W; y.t = W.new_act(L.din, y.H * y.W);
         if (W.live()) W.check(launch_u2d_silu_shuffle((const float*)pre_shuffle.t.p, (float*)y.t.p, B, x.H, x.W, L.din, s));
@@ -387,3 +351,40 @@ int u2d_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
 }
 
 }  // namespace adf_api
+
+extern "C" int adf_unet2d_create(const adf_unet2d_config* cfg, adf_handle** out) {
+    if (create_begin("adf_unet2d_create", cfg, out)) return 1;
+    const adf_unet2d_config& c = *cfg;
+    auto bad = [](const char* m) { g_create_error = std::string("adf_unet2d_create: ") + m; return 1; };
+    if (c.dtype != ADF_DTYPE_F32) return bad("only the exact-fp32 mode (ADF_DTYPE_F32) is built for this net");
+    if (c.n_levels < 1 || c.n_levels > ADF_U2D_MAX_LEVELS || c.num_resnet_blocks < 1) return bad("bad level / block counts");
+    if (c.n_init_kernels < 1 || c.n_init_kernels > ADF_U2D_MAX_INIT_KERNELS) return bad("1 to 4 cross-embed kernel sizes");
+    if (c.channels < 1 || c.channels_out < 1 || c.channels_out > 4) return bad("channels >= 1, 1 <= channels_out <= 4");
+    if (c.dim % 32 || c.dim < 32 || c.dim > 1024 || c.cond_dim < 1 || c.cond_dim > 512 || c.resnet_groups < 1 || c.attn_heads < 1) return bad("bad widths");
+    if (c.num_classes < 0 || (c.num_classes > 0 && (c.cond_dim != c.dim || c.dim > 512))) return bad("class conditioning needs cond_dim == dim <= 512");
+    if (c.learned_sinu_pos_emb_dim < 2 || c.learned_sinu_pos_emb_dim % 2 || c.num_time_tokens < 1) return bad("bad time embedding widths");
+    if (c.layer_attns_depth < 1 || c.layer_mid_attns_depth < 1 || !(c.ff_mult > 0.0)) return bad("bad transformer settings");
+    for (int i = 0; i < c.n_levels; ++i) {
+        const int w = c.dim * c.dim_mults[i];
+        if (c.dim_mults[i] < 1 || w > 512 || w % c.resnet_groups) return bad("level widths must be at most 512 (a skip concat feeds a conv of at most 1024 channels) and multiples of resnet_groups");
+        if (c.layer_attns[i] || c.attend_at_middle) {
+            if (w % c.attn_heads) return bad("attention widths must divide into the heads");
+        }
+    }
+    for (int i = 0; i < c.n_init_kernels; ++i)
+        if (c.init_kernel_sizes[i] < 1 || !(c.init_kernel_sizes[i] & 1) || (i && c.init_kernel_sizes[i] < c.init_kernel_sizes[i - 1])) return bad("cross-embed kernel sizes must be odd and sorted");
+    auto net = std::make_unique<Unet2dNet>();
+    Unet2dNet& u = *net;
+    u.cfg = c;
+    u.init_dim = c.dim; u.tcd = 4 * c.cond_dim;
+    // CrossEmbedLayer's split of init_dim over the sorted kernel sizes (:268-272): init_dim / 2, / 4, ..., the remainder to the largest
+    for (int i = 0; i + 1 < c.n_init_kernels; ++i) u.ce_off[i + 1] = u.ce_off[i] + (c.dim >> (i + 1));
+    u.ce_off[c.n_init_kernels] = c.dim;
+    for (int i = 0; i < c.n_init_kernels; ++i)
+        if (u.ce_off[i + 1] - u.ce_off[i] < 4 || (u.ce_off[i + 1] - u.ce_off[i]) % 4) return bad("every cross-embed slice must be a multiple of 4 channels");
+    // (the label embedder's table has dim columns; with classes, cond_dim == dim was checked above)
+    NetDims& d = u.dims;
+    d.in_channels = c.channels; d.out_channels = c.channels_out;
+    d.temb = u.tcd; d.label_in = c.dim; d.num_classes = c.num_classes; d.stat_groups = c.resnet_groups;
+    return create_finish("adf_unet2d_create", c.dtype, std::move(net), out);
+}

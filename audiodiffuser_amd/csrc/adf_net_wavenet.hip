@@ -1,5 +1,6 @@
-// WaveNetNoise behind the C ABI (reference: src/models/backbones/wavenet.py:153-180): registry, weight-norm packing, the layer walk.
-#include "adf_api_internal.h"
+// WaveNetNoise behind the C ABI (reference: src/models/backbones/wavenet.py:153-180): adf_wavenet_create, registry, weight-norm packing, the
+// layer walk.
+#include "adf_net_wavenet.h"
 
 using namespace adf;
 using namespace adf_api;
@@ -9,9 +10,9 @@ namespace adf_api {
 // ---- WaveNetNoise ----------------------------------------------------------------------------------------------------
 // Registration order = the reference module's state_dict order (wavenet.py:158-167; the custom WeightNorm re-registers
 // g and v after the bias, :37-42).
-int wn_build_weights(adf_handle* h) {
-    WnW& w = *h->wn;
-    const adf_wavenet_config& c = w.cfg;
+int WavenetNet::build_weights(adf_handle* h) {
+    WavenetNet& w = *this;
+    const adf_wavenet_config& c = cfg;
     Registrar R{h};
     const int C = c.residual_channels;
     auto conv = [&](const std::string& pre, WnConv& cv, int cout, int cin, int K, int layout) {
@@ -51,8 +52,9 @@ int wn_build_weights(adf_handle* h) {
 }
 
 // effective weights of every weight-normed conv, as GEMM operands (stream-ordered; the one sumsq scratch is reused in order)
-int wn_pack_weights(adf_handle* h, hipStream_t s) {
-    WnW& w = *h->wn;
+int WavenetNet::prepare(adf_handle* h, hipStream_t s) {
+    if (packed) return 0;
+    WavenetNet& w = *this;
     const int lay = h->bf16 ? 1 : 0;
     auto one = [&](const WnConv& cv, int layout) -> int {
         if (const char* e = launch_wn_sumsq(cv.v, (long long)cv.cout * cv.cin * cv.K, w.sumsq, s)) return fail(h, e);
@@ -67,12 +69,12 @@ int wn_pack_weights(adf_handle* h, hipStream_t s) {
 }
 
 // WaveNetNoise.forward (wavenet.py:169-180) for x [B][1][T]; io as for the U-Net (EDM scalars fused into the first and last kernel)
-int wn_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
-    WnW& w = *h->wn;
-    const adf_wavenet_config& c = w.cfg;
+int WavenetNet::forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
+    WavenetNet& w = *this;
+    const adf_wavenet_config& c = cfg;
     Walker W{h, p, s};
-    p->arena_off = 0; p->stats_off = 0;
-    p->taps.clear(); p->rbs.clear(); p->wn_layers.clear();
+    if (W.begin()) return 1;
+    p->wn_layers.clear();
     const int B = p->B, T = p->L, C = c.residual_channels, NL = c.residual_layers;
     const size_t act = (size_t)B * T * C * h->esz;
     // every layer input stays resident when that is small (the parity taps y<n>); otherwise two buffers alternate
@@ -83,7 +85,7 @@ int wn_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
     if (p->dry) return 0;
     const float* film = io.film_pre ? io.film_pre : p->film;
     if (!io.film_pre) {
-        W.check(launch_wn_step_embed(io.t, io.t_stride, io.nb, w.fc1w, w.fc1b, w.fc2w, w.fc2b, c.dim_in, c.dim_mid, c.dim_out, p->temb, s));
+        W.check(time_embed(io.t, io.t_stride, io.nb, p->temb, s));
         W.check(launch_film(p->temb, c.dim_out, h->film_w, c.dim_out, 0, h->film_b, p->film, io.nb, h->film_total, s));
     }
     WnIO wio;
@@ -116,3 +118,18 @@ int wn_forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
 }
 
 }  // namespace adf_api
+
+extern "C" int adf_wavenet_create(const adf_wavenet_config* cfg, adf_handle** out) {
+    if (create_begin("adf_wavenet_create", cfg, out)) return 1;
+    const adf_wavenet_config& c = *cfg;
+    if (c.residual_channels < 32 || c.residual_channels % 32 || c.residual_channels > 512) { g_create_error = "adf_wavenet_create: residual_channels must be a multiple of 32 in [32, 512]"; return 1; }
+    if (c.residual_layers < 1 || c.residual_layers > 1024 || c.dilation_cycle < 1 || c.dilation_cycle > 24) { g_create_error = "adf_wavenet_create: bad residual_layers / dilation_cycle"; return 1; }
+    if (c.dim_in < 4 || c.dim_in % 2 || c.dim_in > 1024 || c.dim_mid < 1 || c.dim_mid > 1024 || c.dim_out < 4 || c.dim_out % 4 || c.dim_out > 1024) { g_create_error = "adf_wavenet_create: bad embedding widths"; return 1; }
+    if (c.dtype != ADF_DTYPE_F32 && c.dtype != ADF_DTYPE_BF16) { g_create_error = "adf_wavenet_create: bad dtype"; return 1; }
+    if (c.dtype == ADF_DTYPE_BF16 && c.residual_channels != 256 && c.residual_channels != 128 && c.residual_channels != 64) { g_create_error = "adf_wavenet_create: the bf16 (MFMA) kernels are built for residual_channels = 64, 128 or 256; use ADF_DTYPE_F32 for other widths"; return 1; }
+    auto net = std::make_unique<WavenetNet>();
+    net->cfg = c;
+    // one waveform channel in and out, no length constraint, no GroupNorm statistics
+    net->dims.in_channels = 1; net->dims.out_channels = 1; net->dims.temb = c.dim_out;
+    return create_finish("adf_wavenet_create", c.dtype, std::move(net), out);
+}

@@ -15,7 +15,7 @@ int cond_rows(adf_handle* h, int B, bool null_branch, FwdIO& io) {
     if (!h->cond_on || h->cond_B != B)
         return fail(h, "class-conditional network: call adf_set_condition with the labels of this batch first");
     io.null_cond = null_branch;
-    if (h->adm || h->u2d) return 0;  // the ADM net (and UNet2dBase) adds the class embedding to the time embedding before the FiLM projections (adm_forward)
+    if (h->net->class_in_temb) return 0;   // the class embedding joins the time embedding before the FiLM projections, inside the pass (Walk2d::condition)
     if (null_branch) { io.film2 = h->cond_film + (size_t)B * h->film_total; io.film2_bstride = 0; }
     else { io.film2 = h->cond_film; io.film2_bstride = h->film_total; }
     return 0;
@@ -24,7 +24,7 @@ int cond_rows(adf_handle* h, int B, bool null_branch, FwdIO& io) {
 // (allocated outside graph capture: adf_sampler_run calls this before it starts capturing)
 int ensure_cfg_buffers(adf_handle* h, Plan* p) {
     if (p->cfg_c) return 0;
-    const size_t wave = (size_t)p->B * h->cfg.out_channels * p->L;
+    const size_t wave = (size_t)p->B * h->net->dims.out_channels * p->L;
     p->cfg_c = (float*)dalloc(h, wave * 4, p);
     p->cfg_n = (float*)dalloc(h, wave * 4, p);
     if (!p->cfg_c || !p->cfg_n) return fail(h, "device allocation failed for the guidance buffers");
@@ -41,12 +41,12 @@ int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s) {
     const bool noclip = h->unclipped();              // VDiffusion(for_edm=True): no clamp, and dynamic_threshold is stored but never read (diffusion.py:326)
     const bool dyn = h->dyn_q > 0.0f && !noclip;
     // one pass with the preconditioning in the last kernel's epilogue: clamped on every net, unclipped on UNet2dBase (u2d_conv_out_raw_kernel mode 2)
-    if (!cfg && !dyn && (!noclip || h->u2d)) {
+    if (!cfg && !dyn && (!noclip || h->net->unclipped_epilogue)) {
         if (cond_rows(h, p->B, false, io)) return 1;
         io.out = out; io.mode = noclip ? 2 : 1;
         return forward(h, p, io, s);
     }
-    const long long per_sample = (long long)h->cfg.out_channels * p->L;
+    const long long per_sample = (long long)h->net->dims.out_channels * p->L;
     const size_t wave = (size_t)p->B * per_sample;
     if (ensure_cfg_buffers(h, p)) return 1;
     if (dyn && !p->dyn_scale) {
