@@ -48,6 +48,17 @@ class AdfSamplerDesc(C.Structure):
     ]
 
 
+def make_sampler_desc(kind: int, num_steps: int, sigma_data: float, use_graph: bool, **fields) -> AdfSamplerDesc:
+    """The descriptor of one sampler run: what every sampler sets, the neutral value of every other field (no churn window, ``s_noise`` and
+    ``alpha`` 1, every order / flag / ancestral parameter 0), then the sampler's own ``fields``.  The struct's bytes open the hipGraph cache
+    key (adf_api.hip), so a sampler names only what it means to set; tests/test_sampler_host_sweep.py pins the bytes."""
+    unknown = set(fields) - {name for name, _ in AdfSamplerDesc._fields_}
+    if unknown:
+        raise TypeError(f"adf_sampler_desc has no field {sorted(unknown)}")
+    return AdfSamplerDesc(kind=kind, num_steps=int(num_steps), sigma_data=sigma_data, use_graph=int(use_graph),
+                          **{"s_noise": 1.0, "alpha": 1.0, **fields})
+
+
 class AdfWaveNetConfig(C.Structure):
     """``adf_wavenet_config`` of include/audiodiffuser_amd.h."""
     _fields_ = [("residual_channels", C.c_int32), ("residual_layers", C.c_int32), ("dilation_cycle", C.c_int32),

@@ -264,11 +264,7 @@ int adf_denoise(adf_handle* h, const float* x_noisy, const float* sigmas_dev, fl
 }
 
 int adf_sampler_nfe(const adf_sampler_desc* desc, const float* sigmas_host, int n_sigmas) {
-    SamplerCtx c{nullptr, nullptr, desc, sigmas_host, n_sigmas, nullptr, 0};
-    c.count_only = true;
-    float* r = nullptr;
-    if (run_sampler(c, &r)) return -1;
-    return c.nfe;
+    return count_sampler(desc, sigmas_host, n_sigmas);
 }
 
 int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* sigmas_host, int n_sigmas, const float* noise,
@@ -294,11 +290,13 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
         }
     }
     if (hipMemcpyAsync(p->noise_stage, noise, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "noise copy failed");
-    if (injected_noise) {
-        // one draw per step: the EDM sampler steps num_steps times, the DPM2 family num_steps - 1 times
-        const int ndraws = desc->kind == ADF_SAMPLER_ADPMPP2S ? adpmpp2s_draws(sigmas_host, n_sigmas, desc->num_steps)
-                           : (desc->kind == ADF_SAMPLER_DPM2 || desc->kind == ADF_SAMPLER_ADPM2) ? desc->num_steps - 1 : desc->num_steps;
-        const size_t need = (size_t)(ndraws > 0 ? ndraws : 0) * n;
+    const int ndraws = sampler_draws(*desc, sigmas_host, n_sigmas);
+    if (ndraws > 0 && !injected_noise)
+        return fail(h, desc->kind == ADF_SAMPLER_ADPM2 ? "ADPM2Sampler needs injected_noise (one pre-drawn randn_like tensor per step)"
+                       : desc->kind == ADF_SAMPLER_ADPMPP2S ? "ADPMPP2SSampler needs injected_noise (one pre-drawn randn_like tensor per step with sigma_next > 0)"
+                                                            : "a sampler with s_churn > 0 needs injected_noise (pre-drawn randn_like tensors)");
+    if (ndraws > 0) {
+        const size_t need = (size_t)ndraws * n;
         // the ABI carries the number of [B][C][L] draws behind the pointer: a short buffer is an error, not an over-read
         if (n_injected < ndraws)
             return fail(h, "injected_noise holds " + std::to_string(n_injected) + " draws of [B][C][L], this sampler consumes " + std::to_string(ndraws));
@@ -314,23 +312,11 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
             p->inj_cap = need;
         }
         if (hipMemcpyAsync(p->inj_stage, injected_noise, need * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "injected-noise copy failed");
-    } else if ((desc->kind == ADF_SAMPLER_EDM || desc->kind == ADF_SAMPLER_DPM2) && desc->s_churn > 0.f) {
-        return fail(h, "a sampler with s_churn > 0 needs injected_noise (pre-drawn randn_like tensors)");
-    } else if (desc->kind == ADF_SAMPLER_ADPM2) {
-        return fail(h, "ADPM2Sampler needs injected_noise (one pre-drawn randn_like tensor per step)");
-    } else if (desc->kind == ADF_SAMPLER_ADPMPP2S && adpmpp2s_draws(sigmas_host, n_sigmas, desc->num_steps) > 0) {
-        return fail(h, "ADPMPP2SSampler needs injected_noise (one pre-drawn randn_like tensor per step with sigma_next > 0)");
     }
     // the sigma of every denoiser evaluation of this run (host logic only), then the buffers of the per-run table -- sized
     // before any capture starts
     std::vector<float> eval_sigmas;
-    {
-        SamplerCtx cc{nullptr, nullptr, desc, sigmas_host, n_sigmas, nullptr, 0};
-        cc.count_only = true;
-        cc.collect = &eval_sigmas;
-        float* r0 = nullptr;
-        if (run_sampler(cc, &r0)) eval_sigmas.clear();     // a schedule the sampler rejects: the real pass below reports why
-    }
+    if (count_sampler(desc, sigmas_host, n_sigmas, &eval_sigmas) < 0) eval_sigmas.clear();     // a schedule the sampler rejects: the real pass below reports why
     const int n_eval = (int)eval_sigmas.size();
     p->pre_rows = n_eval;
     if (n_eval > p->pre_cap) {

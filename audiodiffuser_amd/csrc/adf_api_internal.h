@@ -1,12 +1,13 @@
 // Internals shared by the translation units behind the C ABI (include/audiodiffuser_amd.h): the handle, the per-(B, L) workspace
-// ("plan"), the weight registry, the network walker.  Round 3 split of what was one 2,400-line adf_api.hip:
+// ("plan"), the weight registry, the network walker, the sampler context.  Round 3 split of what was one 2,400-line adf_api.hip:
 //   adf_api.hip            handle life cycle, weights, workspaces, the extern "C" entry points every network shares
 //   adf_net_unet1d.hip     Unet1dNet: UNet1dBase (unet1d.py:771-816): adf_create, registry, the 1-D walker and its walk
 //   adf_net_wavenet.hip    WavenetNet (declared in adf_net_wavenet.h): WaveNetNoise (wavenet.py:153-180): adf_wavenet_create, registry, walk
 //   adf_net_adm.hip        AdmNet: ADM UNetModel (unet2d_oai.py:382-635): adf_adm_create, registry, walk
 //   adf_net_unet2d.hip     Unet2dNet: Imagen-style UNet2dBase (unet2d.py:622-972), exact fp32: adf_unet2d_create, registry, walk
 //   adf_walk2d.h           what the two 2-D walks share: fine GroupNorm statistics, the conv launch, the conditioning prologue
-//   adf_sampler.hip        denoise wrappers and the sampler state machines (sampler_edm.py, stochastic_sampler_edm.py)
+//   adf_sampler.hip        denoise wrappers; the ten sampler drivers (sampler_edm.py, stochastic_sampler_edm.py), written on SamplerCtx's
+//                          members (below), which own the split between the counting pass and the real pass; count_sampler, sampler_draws
 //   adf_bench_replay.hip   adf_bench_* instrumentation
 // A handle owns one Net (below).  This header, adf_api.hip and adf_sampler.hip know a network only through that interface.
 #pragma once
@@ -328,12 +329,31 @@ int ensure_cfg_buffers(adf_handle* h, Plan* p);
 int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s);
 int denoise_scalar(adf_handle* h, Plan* p, const float* x, float sigma, float sigma_data, float* out, hipStream_t s);
 
+// One run of a sampler driver (adf_sampler.hip).  Every driver runs twice: a host-only counting pass (count_sampler: h == p == nullptr,
+// serves adf_sampler_nfe and the per-run sigma table) and the real pass, which enqueues the launches.  The members below own that split:
+// a driver takes its buffers from buf(), its draws from draw(), launches through start() / run() / finish() and refuses a schedule
+// through reject(), and never asks which pass it is in.
 struct SamplerCtx {
     adf_handle* h; Plan* p; const adf_sampler_desc* d; const float* sig; int nsig; hipStream_t s; long long n;
     int nfe = 0;
     bool count_only = false;
-    std::vector<float>* collect = nullptr;     // count_only pass: the sigma of every evaluation, in order
+    std::vector<float>* collect = nullptr;     // counting pass: the sigma of every evaluation, in order
     bool precomputed = false;                  // real pass: evaluation k reads row k of Plan::coef_all / film_all
+    int ck(const char* e) { if (e) { h->err = e; return 1; } return 0; }
+    float* buf(int k) const { return count_only ? nullptr : p->sb[k]; }                 // state buffer k (fp32 [B][C][L])
+    int reject(const std::string& msg) { return count_only ? 1 : fail(h, msg); }         // a schedule / descriptor the driver does not run
+    // one launch of adf_kernels.h: every sampler launcher ends in (..., long long n, hipStream_t s)
+    template <class F, class... A> int run(F launcher, A... args) { return count_only ? 0 : ck(launcher(args..., n, s)); }
+    int start(float* x) { return count_only ? 0 : ck(launch_scale(x, p->noise_stage, sig[0], n, s)); }      // x = sigmas[0] * noise
+    int finish(float* x, float** result) { *result = x; return run(launch_clamp, x); }                       // the loops that end in clamp(-1, 1)
+    // draw k of the injected noise; the real pass refuses with `needs` when the caller passed none
+    int draw(int k, const char* needs, const float** eps) {
+        *eps = nullptr;
+        if (count_only) return 0;
+        if (!p->inj_stage) return fail(h, needs);
+        *eps = p->inj_stage + (size_t)k * n;
+        return 0;
+    }
     int den(const float* x, float sigma, float* out) {
         const int k = nfe++;
         if (count_only) { if (collect) collect->push_back(sigma); return 0; }
@@ -347,7 +367,6 @@ struct SamplerCtx {
         }
         return denoise_scalar(h, p, x, sigma, d->sigma_data, out, s);
     }
-    int ck(const char* e) { if (e) { h->err = e; return 1; } return 0; }
     // DPMSampler.model_fn (sampler_edm.py:692-708): the denoised estimate, or with eps_pred the noise prediction (x - D) / sigma
     int model(const float* x, float sigma, float* out) {
         if (den(x, sigma, out)) return 1;
@@ -356,6 +375,9 @@ struct SamplerCtx {
     }
 };
 int run_sampler(SamplerCtx& c, float** result);
-int adpmpp2s_draws(const float* sig, int nsig, int N);      // randn_like draws ADPMPP2SSampler consumes on this schedule
+// the counting pass: NFE of this sampler on this schedule, or -1 where its driver rejects it; eval_sigmas: the sigma of every evaluation, in order
+int count_sampler(const adf_sampler_desc* d, const float* sig, int nsig, std::vector<float>* eval_sigmas = nullptr);
+// [B][C][L] draws of the injected noise the driver reads on this schedule (0: the sampler runs without injected_noise)
+int sampler_draws(const adf_sampler_desc& d, const float* sig, int nsig);
 
 }  // namespace adf_api

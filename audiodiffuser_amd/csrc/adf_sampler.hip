@@ -77,42 +77,43 @@ int denoise_scalar(adf_handle* h, Plan* p, const float* x, float sigma, float si
 }
 
 // ---- sampler drivers -----------------------------------------------------------------------------------
+// Each returns the buffer holding the final sample through *result.  Written on SamplerCtx's members (adf_api_internal.h), so the same
+// code is the counting pass and the real pass.
 
-// returns the buffer holding the final sample through *result
+// The EDM churn of one step (sampler_edm.py:346-356; DPM2Sampler :439-447): s_hat = sigma + gamma sigma and, where gamma > 0,
+// xh = x + sqrt(s_hat^2 - sigma^2) s_noise eps with draw i; otherwise s_hat = sigma (what sigma + 0 * sigma is for every finite sigma) and xh = x.
+static int churn_step(SamplerCtx& c, const char* needs, int i, float* X, float* XH, float* s_hat, const float** xh) {
+    const adf_sampler_desc& d = *c.d;
+    const float gmax = fminf(d.s_churn / (float)d.num_steps, (float)(std::sqrt(2.0) - 1.0));
+    const float sg = c.sig[i];
+    const float gamma = (sg >= d.s_tmin && sg <= d.s_tmax) ? gmax : 0.0f;
+    *s_hat = sg; *xh = X;
+    if (!(gamma > 0.f)) return 0;
+    *s_hat = sg + gamma * sg;
+    const float cc = sqrtf(*s_hat * *s_hat - sg * sg);
+    const float* eps;
+    if (c.draw(i, needs, &eps) || c.run(launch_churn, XH, X, eps, cc, d.s_noise)) return 1;
+    *xh = XH;
+    return 0;
+}
+
 int run_edm(SamplerCtx& c, float** result) {
     const adf_sampler_desc& d = *c.d;
     const int N = d.num_steps;
-    if (c.nsig < N) return c.count_only ? 1 : fail(c.h, "EDMSampler: need at least num_steps sigmas");
-    Plan* p = c.p;
-    float* X = c.count_only ? nullptr : p->sb[0];
-    float* XN = c.count_only ? nullptr : p->sb[1];
-    float* XH = c.count_only ? nullptr : p->sb[2];
-    float* XE = c.count_only ? nullptr : p->sb[3];
-    float* D = c.count_only ? nullptr : p->sb[4];
-    float* DEN = c.count_only ? nullptr : p->sb[5];
-    if (!c.count_only && c.ck(launch_scale(X, p->noise_stage, c.sig[0], c.n, c.s))) return 1;
-    const float gmax = fminf(d.s_churn / (float)N, (float)(std::sqrt(2.0) - 1.0));
+    if (c.nsig < N) return c.reject("EDMSampler: need at least num_steps sigmas");
+    float *X = c.buf(0), *XN = c.buf(1), *XH = c.buf(2), *XE = c.buf(3), *D = c.buf(4), *DEN = c.buf(5);
+    if (c.start(X)) return 1;
     for (int i = 0; i < N; ++i) {
-        const float sg = c.sig[i];
         const float sn = (i + 1 < c.nsig) ? c.sig[i + 1] : 0.0f;
-        const float gamma = (sg >= d.s_tmin && sg <= d.s_tmax) ? gmax : 0.0f;
-        float s_hat = sg;
-        const float* xh = X;
-        if (gamma > 0.f) {
-            s_hat = sg + gamma * sg;
-            const float cc = sqrtf(s_hat * s_hat - sg * sg);
-            if (!c.count_only) {
-                if (!p->inj_stage) return fail(c.h, "EDMSampler with churn needs injected_noise");
-                if (c.ck(launch_churn(XH, X, p->inj_stage + (size_t)i * c.n, cc, d.s_noise, c.n, c.s))) return 1;
-            }
-            xh = XH;
-        }
+        float s_hat;
+        const float* xh;
+        if (churn_step(c, "EDMSampler with churn needs injected_noise", i, X, XH, &s_hat, &xh)) return 1;
         if (c.den(xh, s_hat, DEN)) return 1;
         const float dt = sn - s_hat;
-        if (!c.count_only && c.ck(launch_euler(XE, D, xh, DEN, s_hat, dt, c.n, c.s))) return 1;
+        if (c.run(launch_euler, XE, D, xh, DEN, s_hat, dt)) return 1;
         if (sn != 0.f && d.use_heun) {
             if (c.den(XE, sn, DEN)) return 1;
-            if (!c.count_only && c.ck(launch_rk2(XN, xh, D, XE, DEN, sn, 0.5f * dt, 1.0f, 1.0f, c.n, c.s))) return 1;
+            if (c.run(launch_rk2, XN, xh, D, XE, DEN, sn, 0.5f * dt, 1.0f, 1.0f)) return 1;
             std::swap(X, XN);
         } else {
             std::swap(X, XE);
@@ -125,14 +126,9 @@ int run_edm(SamplerCtx& c, float** result) {
 int run_edm_alpha(SamplerCtx& c, float** result) {
     const adf_sampler_desc& d = *c.d;
     const int N = d.num_steps;
-    if (c.nsig < N) return c.count_only ? 1 : fail(c.h, "EDMAlphaSampler: need at least num_steps sigmas");
-    Plan* p = c.p;
-    float* X = c.count_only ? nullptr : p->sb[0];
-    float* XN = c.count_only ? nullptr : p->sb[1];
-    float* XE = c.count_only ? nullptr : p->sb[3];
-    float* D = c.count_only ? nullptr : p->sb[4];
-    float* DEN = c.count_only ? nullptr : p->sb[5];
-    if (!c.count_only && c.ck(launch_scale(X, p->noise_stage, c.sig[0], c.n, c.s))) return 1;
+    if (c.nsig < N) return c.reject("EDMAlphaSampler: need at least num_steps sigmas");
+    float *X = c.buf(0), *XN = c.buf(1), *XE = c.buf(3), *D = c.buf(4), *DEN = c.buf(5);
+    if (c.start(X)) return 1;
     const float alpha = d.alpha;
     for (int i = 0; i + 1 < N; ++i) {
         const float sg = c.sig[i], sn = c.sig[i + 1];
@@ -140,13 +136,13 @@ int run_edm_alpha(SamplerCtx& c, float** result) {
         if (c.den(X, sg, DEN)) return 1;
         const float sp = sg + alpha * hh;
         if (sp != 0.f && d.use_heun) {
-            if (!c.count_only && c.ck(launch_euler(XE, D, X, DEN, sg, alpha * hh, c.n, c.s))) return 1;
+            if (c.run(launch_euler, XE, D, X, DEN, sg, alpha * hh)) return 1;
             if (c.den(XE, sp, DEN)) return 1;
             const float w1 = (float)(1.0 - 0.5 / (double)alpha), w2 = (float)(0.5 / (double)alpha);
-            if (!c.count_only && c.ck(launch_rk2(XN, X, D, XE, DEN, sp, hh, w1, w2, c.n, c.s))) return 1;
+            if (c.run(launch_rk2, XN, X, D, XE, DEN, sp, hh, w1, w2)) return 1;
             std::swap(X, XN);
         } else {
-            if (!c.count_only && c.ck(launch_euler(XE, D, X, DEN, sg, hh, c.n, c.s))) return 1;
+            if (c.run(launch_euler, XE, D, X, DEN, sg, hh)) return 1;
             std::swap(X, XE);
         }
     }
@@ -176,20 +172,24 @@ DpmGrid dpm_grid(const float* sig, int nsig, int n, bool logsp) {
         r.g[i] = i < steps / 2 ? start + step * (float)i : end - step * (float)(steps - 1 - i);
     return r;
 }
+// What the three grid solvers (DPMSampler multistep / single-step, UniPCSampler) check first: the order, then `steps` against the
+// steps the solver needs and the schedule against the sigmas it reads.
+static int check_grid_solver(SamplerCtx& c, const std::string& who, int steps, int min_steps, int min_sigmas) {
+    if (c.d->order < 1 || c.d->order > 3) return c.reject(who + ": order must be 1, 2 or 3");
+    if (steps < min_steps || c.nsig < min_sigmas) return c.reject(who + ": not enough steps / sigmas");
+    return 0;
+}
 
 int run_dpm(SamplerCtx& c, float** result) {
     const adf_sampler_desc& d = *c.d;
     const bool logsp = d.log_time_spacing != 0;
     const int steps = logsp ? d.num_steps : d.num_steps - 1;  // sampler_edm.py:526
     const int order = d.order;
-    if (order < 1 || order > 3) return c.count_only ? 1 : fail(c.h, "DPMSampler: order must be 1, 2 or 3");
-    if (steps < order || c.nsig < 2 || (!logsp && c.nsig < steps + 1)) return c.count_only ? 1 : fail(c.h, "DPMSampler: not enough steps / sigmas");
+    if (check_grid_solver(c, "DPMSampler", steps, order, logsp ? 2 : std::max(2, steps + 1))) return 1;
     const DpmGrid G = dpm_grid(c.sig, c.nsig, steps, logsp);
-    Plan* p = c.p;
-    float* X = c.count_only ? nullptr : p->sb[0];
-    float* XN = c.count_only ? nullptr : p->sb[1];
-    float* M[3] = {c.count_only ? nullptr : p->sb[6], c.count_only ? nullptr : p->sb[7], c.count_only ? nullptr : p->sb[8]};
-    if (!c.count_only && c.ck(launch_scale(X, p->noise_stage, c.sig[0], c.n, c.s))) return 1;
+    float *X = c.buf(0), *XN = c.buf(1);
+    float* M[3] = {c.buf(6), c.buf(7), c.buf(8)};
+    if (c.start(X)) return 1;
     // history of grid values: index 0 = most recent
     float sh[3] = {G.g[0], 0.f, 0.f};
     const bool eps = d.eps_pred != 0;
@@ -228,7 +228,7 @@ int run_dpm(SamplerCtx& c, float** result) {
             }
         }
         const int last = step == steps;
-        if (!c.count_only && c.ck(launch_dpm_update(XN, X, a, last, c.n, c.s))) return 1;
+        if (c.run(launch_dpm_update, XN, X, a, last)) return 1;
         std::swap(X, XN);
         sh[2] = sh[1]; sh[1] = sh[0]; sh[0] = sc;
         if (!last) {
@@ -249,8 +249,7 @@ int run_dpm_single(SamplerCtx& c, float** result) {
     const bool logsp = d.log_time_spacing != 0;
     const int n_eff = logsp ? d.num_steps : d.num_steps - 1;
     const int order = d.order;
-    if (order < 1 || order > 3) return c.count_only ? 1 : fail(c.h, "DPMSampler: order must be 1, 2 or 3");
-    if (n_eff < 1 || c.nsig < 2) return c.count_only ? 1 : fail(c.h, "DPMSampler: not enough steps / sigmas");
+    if (check_grid_solver(c, "DPMSampler", n_eff, 1, 2)) return 1;
     std::vector<int> orders;
     int K;
     if (order == 3) {
@@ -265,18 +264,12 @@ int run_dpm_single(SamplerCtx& c, float** result) {
         K = n_eff;
         orders.assign(n_eff, 1);
     }
-    if (!logsp && c.nsig < (int)orders.size() + 1) return c.count_only ? 1 : fail(c.h, "DPMSampler: fewer sigmas than solver intervals");
+    if (!logsp && c.nsig < (int)orders.size() + 1) return c.reject("DPMSampler: fewer sigmas than solver intervals");
     const DpmGrid G = dpm_grid(c.sig, c.nsig, K, logsp);
-    Plan* p = c.p;
-    float* X = c.count_only ? nullptr : p->sb[0];
-    float* XN = c.count_only ? nullptr : p->sb[1];
-    float* U = c.count_only ? nullptr : p->sb[2];
-    float* E0 = c.count_only ? nullptr : p->sb[6];
-    float* E1 = c.count_only ? nullptr : p->sb[7];
-    float* E2 = c.count_only ? nullptr : p->sb[8];
-    if (!c.count_only && c.ck(launch_scale(X, p->noise_stage, c.sig[0], c.n, c.s))) return 1;
+    float *X = c.buf(0), *XN = c.buf(1), *U = c.buf(2), *E0 = c.buf(6), *E1 = c.buf(7), *E2 = c.buf(8);
+    if (c.start(X)) return 1;
     auto comb = [&](float* out, const float* e1, float a, float b, float cc, int clampit) -> int {
-        return c.count_only ? 0 : c.ck(launch_lincomb(out, X, E0, e1, a, b, cc, clampit, c.n, c.s));
+        return c.run(launch_lincomb, out, X, E0, e1, a, b, cc, clampit);
     };
     for (size_t i = 0; i < orders.size(); ++i) {
         const float cur = G.g[i], nxt = G.g[i + 1];
@@ -338,36 +331,32 @@ int run_dpm_single(SamplerCtx& c, float** result) {
 int run_dpm2m(SamplerCtx& c, float** result) {
     const adf_sampler_desc& d = *c.d;
     const int N = d.num_steps;
-    if (N < 1 || c.nsig < N + 1) return c.count_only ? 1 : fail(c.h, "DPM2MSampler: the schedule must hold num_steps + 1 sigmas (the reference indexes sigmas[i + 1])");
-    Plan* p = c.p;
-    float* X = c.count_only ? nullptr : p->sb[0];
-    float* XN = c.count_only ? nullptr : p->sb[1];
-    float* D[2] = {c.count_only ? nullptr : p->sb[5], c.count_only ? nullptr : p->sb[6]};
-    if (!c.count_only && c.ck(launch_scale(X, p->noise_stage, c.sig[0], c.n, c.s))) return 1;
+    if (N < 1 || c.nsig < N + 1) return c.reject("DPM2MSampler: the schedule must hold num_steps + 1 sigmas (the reference indexes sigmas[i + 1])");
+    float *X = c.buf(0), *XN = c.buf(1);
+    float* D[2] = {c.buf(5), c.buf(6)};
+    if (c.start(X)) return 1;
     for (int i = 0; i < N; ++i) {
         const float sg = c.sig[i], sn = c.sig[i + 1];
         float* den = D[i & 1];
         const float* old = i > 0 ? D[(i + 1) & 1] : nullptr;
         if (c.den(X, sg, den)) return 1;
-        if (d.reflow && !c.count_only && c.ck(launch_reflow(den, X, sg, c.n, c.s))) return 1;     // stochastic_sampler_edm.py:214-215
+        if (d.reflow && c.run(launch_reflow, den, X, sg)) return 1;     // stochastic_sampler_edm.py:214-215
         const float t = -logf(sg), tn = -logf(sn);
         const float h = tn - t;
         const float ratio = fminf(expf(-tn), expf(-t)) / fmaxf(expf(-tn), expf(-t));
         if (!old || sn == 0.0f) {
-            if (!c.count_only && c.ck(launch_dpm2m(XN, X, den, nullptr, ratio, expm1f(-h), 1.f, 0.f, c.n, c.s))) return 1;
+            if (c.run(launch_dpm2m, XN, X, den, nullptr, ratio, expm1f(-h), 1.f, 0.f)) return 1;
         } else {
             const float h_last = t - (-logf(c.sig[i - 1]));
             const float h_min = fminf(h_last, h), h_max = fmaxf(h_last, h);
             const float r = h_max / h_min;
             const float h_d = (h_max + h_min) / 2.0f;
             const float c2 = 1.0f / (2.0f * r);
-            if (!c.count_only && c.ck(launch_dpm2m(XN, X, den, old, ratio, expm1f(-h_d), 1.0f + c2, c2, c.n, c.s))) return 1;
+            if (c.run(launch_dpm2m, XN, X, den, old, ratio, expm1f(-h_d), 1.0f + c2, c2)) return 1;
         }
         std::swap(X, XN);
     }
-    if (!c.count_only && c.ck(launch_clamp(X, c.n, c.s))) return 1;
-    *result = X;
-    return 0;
+    return c.finish(X, result);
 }
 
 // LMSSampler.linear_multistep_coeff (sampler_edm.py:1149-1160): the integral over [t_i, t_{i+1}] of the Lagrange basis
@@ -394,14 +383,11 @@ double lms_coeff(int order, const float* t, int i, int j) {
 int run_lms(SamplerCtx& c, float** result) {
     const adf_sampler_desc& d = *c.d;
     const int N = d.num_steps, order = d.order;
-    if (order < 1 || order > 4) return c.count_only ? 1 : fail(c.h, "LMSSampler: order must be 1..4");
-    if (N < 2 || c.nsig < N) return c.count_only ? 1 : fail(c.h, "LMSSampler: need at least num_steps (>= 2) sigmas");
-    Plan* p = c.p;
-    float* X = c.count_only ? nullptr : p->sb[0];
-    float* DEN = c.count_only ? nullptr : p->sb[5];
-    float* D[4] = {nullptr, nullptr, nullptr, nullptr};
-    if (!c.count_only) { D[0] = p->sb[1]; D[1] = p->sb[2]; D[2] = p->sb[3]; D[3] = p->sb[4]; }
-    if (!c.count_only && c.ck(launch_scale(X, p->noise_stage, c.sig[0], c.n, c.s))) return 1;
+    if (order < 1 || order > 4) return c.reject("LMSSampler: order must be 1..4");
+    if (N < 2 || c.nsig < N) return c.reject("LMSSampler: need at least num_steps (>= 2) sigmas");
+    float *X = c.buf(0), *DEN = c.buf(5);
+    float* D[4] = {c.buf(1), c.buf(2), c.buf(3), c.buf(4)};
+    if (c.start(X)) return 1;
     for (int i = 0; i + 1 < N; ++i) {
         if (c.den(X, c.sig[i], DEN)) return 1;
         const int cur = std::min(i + 1, order);
@@ -411,11 +397,9 @@ int run_lms(SamplerCtx& c, float** result) {
         for (int j = 0; j < cur; ++j) a.c[j] = (float)lms_coeff(cur, c.sig, i, j);
         a.dcur = D[i & 3];
         a.d1 = D[(i + 3) & 3]; a.d2 = D[(i + 2) & 3]; a.d3 = D[(i + 1) & 3];
-        if (!c.count_only && c.ck(launch_lms(X, DEN, c.sig[i], a, c.n, c.s))) return 1;
+        if (c.run(launch_lms, X, DEN, c.sig[i], a)) return 1;
     }
-    if (!c.count_only && c.ck(launch_clamp(X, c.n, c.s))) return 1;
-    *result = X;
-    return 0;
+    return c.finish(X, result);
 }
 
 // DPM2Sampler: sampler_edm.py:470-493 (loop over num_steps-1 steps, final clamp), :428-468 (step).  As written in
@@ -423,124 +407,95 @@ int run_lms(SamplerCtx& c, float** result) {
 int run_dpm2(SamplerCtx& c, float** result) {
     const adf_sampler_desc& d = *c.d;
     const int N = d.num_steps;
-    if (N < 2 || c.nsig < N) return c.count_only ? 1 : fail(c.h, "DPM2Sampler: need at least num_steps (>= 2) sigmas");
-    Plan* p = c.p;
-    float* X = c.count_only ? nullptr : p->sb[0];
-    float* XN = c.count_only ? nullptr : p->sb[1];
-    float* XH = c.count_only ? nullptr : p->sb[2];
-    float* X2 = c.count_only ? nullptr : p->sb[3];
-    float* DEN = c.count_only ? nullptr : p->sb[5];
-    if (!c.count_only && c.ck(launch_scale(X, p->noise_stage, c.sig[0], c.n, c.s))) return 1;
-    const float gmax = fminf(d.s_churn / (float)N, (float)(std::sqrt(2.0) - 1.0));
+    if (N < 2 || c.nsig < N) return c.reject("DPM2Sampler: need at least num_steps (>= 2) sigmas");
+    float *X = c.buf(0), *XN = c.buf(1), *XH = c.buf(2), *X2 = c.buf(3), *DEN = c.buf(5);
+    if (c.start(X)) return 1;
     for (int i = 0; i + 1 < N; ++i) {
-        const float sg = c.sig[i], sn = c.sig[i + 1];
-        const float gamma = (sg >= d.s_tmin && sg <= d.s_tmax) ? gmax : 0.0f;
-        const float s_hat = sg + gamma * sg;
-        const float* xh = X;
-        if (gamma > 0.f) {
-            if (!c.count_only) {
-                if (!p->inj_stage) return fail(c.h, "DPM2Sampler with churn needs injected_noise");
-                const float cc = sqrtf(s_hat * s_hat - sg * sg);
-                if (c.ck(launch_churn(XH, X, p->inj_stage + (size_t)i * c.n, cc, d.s_noise, c.n, c.s))) return 1;
-            }
-            xh = XH;
-        }
+        const float sn = c.sig[i + 1];
+        float s_hat;
+        const float* xh;
+        if (churn_step(c, "DPM2Sampler with churn needs injected_noise", i, X, XH, &s_hat, &xh)) return 1;
         if (c.den(xh, s_hat, DEN)) return 1;
         if (sn == 0.0f) {
-            if (!c.count_only && c.ck(launch_dstep(XN, X, xh, DEN, s_hat, sn - s_hat, c.n, c.s))) return 1;
+            if (c.run(launch_dstep, XN, X, xh, DEN, s_hat, sn - s_hat)) return 1;
         } else {
             const float lh = logf(s_hat), ln = logf(sn);
             const float s_mid = expf(lh + 0.5f * (ln - lh));                 // log().lerp(log(), 0.5).exp() in fp32
-            if (!c.count_only && c.ck(launch_dstep(X2, X, xh, DEN, s_hat, s_mid - s_hat, c.n, c.s))) return 1;
+            if (c.run(launch_dstep, X2, X, xh, DEN, s_hat, s_mid - s_hat)) return 1;
             if (c.den(X2, s_mid, DEN)) return 1;
-            if (!c.count_only && c.ck(launch_dstep(XN, X, X2, DEN, s_mid, sn - s_hat, c.n, c.s))) return 1;
+            if (c.run(launch_dstep, XN, X, X2, DEN, s_mid, sn - s_hat)) return 1;
         }
         std::swap(X, XN);
     }
-    if (!c.count_only && c.ck(launch_clamp(X, c.n, c.s))) return 1;
-    *result = X;
-    return 0;
+    return c.finish(X, result);
 }
 
-// ADPM2Sampler: stochastic_sampler_edm.py:85-100 (loop, final clamp), :53-83 (step), :29-32 (get_sigmas); fp32 scalars
+// get_sigmas of the two ancestral samplers (stochastic_sampler_edm.py:29-32), fp32 scalars
+static void ancestral_sigmas(float eta, float sg, float sn, float* s_up, float* s_down) {
+    const float up_raw = eta * sqrtf(sn * sn * (sg * sg - sn * sn) / (sg * sg));
+    *s_up = sn < up_raw ? sn : up_raw;                                         // python min(sigma_next, ...)
+    *s_down = sqrtf(sn * sn - *s_up * *s_up);
+}
+
+// ADPM2Sampler: stochastic_sampler_edm.py:85-100 (loop, final clamp), :53-83 (step); one draw per step
 int run_adpm2(SamplerCtx& c, float** result) {
     const adf_sampler_desc& d = *c.d;
     const int N = d.num_steps;
-    if (N < 2 || c.nsig < N) return c.count_only ? 1 : fail(c.h, "ADPM2Sampler: need at least num_steps (>= 2) sigmas");
-    if (!(d.rho > 0.f)) return c.count_only ? 1 : fail(c.h, "ADPM2Sampler: rho must be positive");
-    Plan* p = c.p;
-    float* X = c.count_only ? nullptr : p->sb[0];
-    float* XN = c.count_only ? nullptr : p->sb[1];
-    float* XM = c.count_only ? nullptr : p->sb[3];
-    float* DEN = c.count_only ? nullptr : p->sb[5];
-    if (!c.count_only && !p->inj_stage) return fail(c.h, "ADPM2Sampler needs injected_noise (one draw per step)");
-    if (!c.count_only && c.ck(launch_scale(X, p->noise_stage, c.sig[0], c.n, c.s))) return 1;
+    if (N < 2 || c.nsig < N) return c.reject("ADPM2Sampler: need at least num_steps (>= 2) sigmas");
+    if (!(d.rho > 0.f)) return c.reject("ADPM2Sampler: rho must be positive");
+    float *X = c.buf(0), *XN = c.buf(1), *XM = c.buf(3), *DEN = c.buf(5);
+    if (c.start(X)) return 1;
     for (int i = 0; i + 1 < N; ++i) {
         const float sg = c.sig[i], sn = c.sig[i + 1];
-        const float up_raw = d.eta * sqrtf(sn * sn * (sg * sg - sn * sn) / (sg * sg));
-        const float s_up = sn < up_raw ? sn : up_raw;                          // python min(sigma_next, ...)
-        const float s_down = sqrtf(sn * sn - s_up * s_up);
+        float s_up, s_down;
+        ancestral_sigmas(d.eta, sg, sn, &s_up, &s_down);
         const float inv = 1.0f / d.rho;
         const float s_mid = powf((powf(sg, inv) + powf(s_down, inv)) / 2.0f, d.rho);
         if (c.den(X, sg, DEN)) return 1;
-        if (!c.count_only && c.ck(launch_dstep(XM, X, X, DEN, sg, s_mid - sg, c.n, c.s))) return 1;
+        if (c.run(launch_dstep, XM, X, X, DEN, sg, s_mid - sg)) return 1;
         if (c.den(XM, s_mid, DEN)) return 1;
-        if (!c.count_only) {
-            if (c.ck(launch_dstep(XN, X, XM, DEN, s_mid, s_down - sg, c.n, c.s))) return 1;
-            if (c.ck(launch_churn(X, XN, p->inj_stage + (size_t)i * c.n, s_up, 1.0f, c.n, c.s))) return 1;   // x + sigma_up * randn
-        }
+        if (c.run(launch_dstep, XN, X, XM, DEN, s_mid, s_down - sg)) return 1;
+        const float* eps;
+        if (c.draw(i, "ADPM2Sampler needs injected_noise (one draw per step)", &eps)) return 1;
+        if (c.run(launch_churn, X, XN, eps, s_up, 1.0f)) return 1;           // x + sigma_up * randn
     }
-    if (!c.count_only && c.ck(launch_clamp(X, c.n, c.s))) return 1;
-    *result = X;
-    return 0;
+    return c.finish(X, result);
 }
 
-// ADPMPP2SSampler: stochastic_sampler_edm.py:162-178 (loop, final clamp), :117-160 (step), :29-32 (get_sigmas); fp32 scalars.  A draw is
-// consumed only by a step whose sigma_next is positive (:158): adpmpp2s_draws() counts them for the injected-noise check.
-int adpmpp2s_draws(const float* sig, int nsig, int N) {
-    int k = 0;
-    for (int i = 0; i + 1 < N && i + 1 < nsig; ++i) k += sig[i + 1] > 0.0f;
-    return k;
-}
+// ADPMPP2SSampler: stochastic_sampler_edm.py:162-178 (loop, final clamp), :117-160 (step); fp32 scalars.  A draw is
+// consumed only by a step whose sigma_next is positive (:158): sampler_draws() counts them.
 int run_adpmpp2s(SamplerCtx& c, float** result) {
     const adf_sampler_desc& d = *c.d;
     const int N = d.num_steps;
-    if (N < 2 || c.nsig < N) return c.count_only ? 1 : fail(c.h, "ADPMPP2SSampler: need at least num_steps (>= 2) sigmas");
-    Plan* p = c.p;
-    float* X = c.count_only ? nullptr : p->sb[0];
-    float* XN = c.count_only ? nullptr : p->sb[1];
-    float* X2 = c.count_only ? nullptr : p->sb[3];
-    float* DEN = c.count_only ? nullptr : p->sb[5];
-    if (!c.count_only && !p->inj_stage && adpmpp2s_draws(c.sig, c.nsig, N) > 0) return fail(c.h, "ADPMPP2SSampler needs injected_noise (one draw per step with sigma_next > 0)");
-    if (!c.count_only && c.ck(launch_scale(X, p->noise_stage, c.sig[0], c.n, c.s))) return 1;
+    if (N < 2 || c.nsig < N) return c.reject("ADPMPP2SSampler: need at least num_steps (>= 2) sigmas");
+    float *X = c.buf(0), *XN = c.buf(1), *X2 = c.buf(3), *DEN = c.buf(5);
+    if (c.start(X)) return 1;
     int k = 0;
     for (int i = 0; i + 1 < N; ++i) {
         const float sg = c.sig[i], sn = c.sig[i + 1];
-        const float up_raw = d.eta * sqrtf(sn * sn * (sg * sg - sn * sn) / (sg * sg));
-        const float s_up = sn < up_raw ? sn : up_raw;                          // python min(sigma_next, ...)
-        const float s_down = sqrtf(sn * sn - s_up * s_up);
+        float s_up, s_down;
+        ancestral_sigmas(d.eta, sg, sn, &s_up, &s_down);
         if (c.den(X, sg, DEN)) return 1;
         if (s_down == 0.0f) {                                                  // Euler step to sigma_down (:136-140)
-            if (!c.count_only && c.ck(launch_dstep(XN, X, X, DEN, sg, s_down - sg, c.n, c.s))) return 1;
+            if (c.run(launch_dstep, XN, X, X, DEN, sg, s_down - sg)) return 1;
         } else {
             const float t = -logf(sg), tn = -logf(s_down);
             const float h = tn - t;
             const float sm = t + 0.5f * h;
             const float sig_mid = expf(-sm);
-            if (!c.count_only && c.ck(launch_dpm2m(X2, X, DEN, nullptr, sig_mid / expf(-t), expm1f(-h * 0.5f), 1.f, 0.f, c.n, c.s))) return 1;
+            if (c.run(launch_dpm2m, X2, X, DEN, nullptr, sig_mid / expf(-t), expm1f(-h * 0.5f), 1.f, 0.f)) return 1;
             if (c.den(X2, sig_mid, DEN)) return 1;
-            if (!c.count_only && c.ck(launch_dpm2m(XN, X, DEN, nullptr, expf(-tn) / expf(-t), expm1f(-h), 1.f, 0.f, c.n, c.s))) return 1;
+            if (c.run(launch_dpm2m, XN, X, DEN, nullptr, expf(-tn) / expf(-t), expm1f(-h), 1.f, 0.f)) return 1;
         }
         if (sn > 0.0f) {
-            if (!c.count_only && c.ck(launch_churn(X, XN, p->inj_stage + (size_t)k * c.n, s_up, 1.0f, c.n, c.s))) return 1;   // x + sigma_up * randn
-            ++k;
+            const float* eps;
+            if (c.draw(k++, "ADPMPP2SSampler needs injected_noise (one draw per step with sigma_next > 0)", &eps)) return 1;
+            if (c.run(launch_churn, X, XN, eps, s_up, 1.0f)) return 1;       // x + sigma_up * randn
         } else {
             std::swap(X, XN);
         }
     }
-    if (!c.count_only && c.ck(launch_clamp(X, c.n, c.s))) return 1;
-    *result = X;
-    return 0;
+    return c.finish(X, result);
 }
 
 // UniPCSampler.forward (sampler_edm.py:996-1053, variant 'bh2').  Every coefficient depends on the grid only: computed on the host
@@ -570,15 +525,11 @@ int run_unipc(SamplerCtx& c, float** result) {
     const bool logsp = d.log_time_spacing != 0, eps = d.eps_pred != 0;
     const int steps = logsp ? d.num_steps : d.num_steps - 1;          // :828
     const int order = d.order;
-    if (order < 1 || order > 3) return c.count_only ? 1 : fail(c.h, "UniPCSampler: order must be 1, 2 or 3");
-    if (steps < order || c.nsig < 2 || (!logsp && c.nsig < steps + 1)) return c.count_only ? 1 : fail(c.h, "UniPCSampler: not enough steps / sigmas");
+    if (check_grid_solver(c, "UniPCSampler", steps, order, logsp ? 2 : std::max(2, steps + 1))) return 1;
     const DpmGrid G = dpm_grid(c.sig, c.nsig, steps, logsp);
-    Plan* p = c.p;
-    float* X = c.count_only ? nullptr : p->sb[0];
-    float* XN = c.count_only ? nullptr : p->sb[1];
-    float* XT = c.count_only ? nullptr : p->sb[2];
-    float* MB[4] = {c.count_only ? nullptr : p->sb[6], c.count_only ? nullptr : p->sb[7], c.count_only ? nullptr : p->sb[8], c.count_only ? nullptr : p->sb[9]};
-    if (!c.count_only && c.ck(launch_scale(X, p->noise_stage, c.sig[0], c.n, c.s))) return 1;
+    float *X = c.buf(0), *XN = c.buf(1), *XT = c.buf(2);
+    float* MB[4] = {c.buf(6), c.buf(7), c.buf(8), c.buf(9)};
+    if (c.start(X)) return 1;
     // history, oldest first (as the reference's lists); a free buffer of MB receives the next model value
     std::vector<float*> ml; std::vector<float> gl;
     auto free_buf = [&]() -> float* { for (float* b : MB) if (std::find(ml.begin(), ml.end(), b) == ml.end()) return b; return MB[0]; };
@@ -624,7 +575,7 @@ int run_unipc(SamplerCtx& c, float** result) {
         u.mt = nullptr;
         float* xin = *x_io;
         float* xt = corr ? XT : (xin == X ? XN : X);
-        if (!c.count_only && c.ck(launch_unipc(xt, xin, u, c.n, c.s))) return 1;      // predictor (:951-957 / :973-979)
+        if (c.run(launch_unipc, xt, xin, u)) return 1;      // predictor (:951-957 / :973-979)
         *m_out = nullptr;
         if (corr) {
             float* mt = free_buf();
@@ -632,7 +583,7 @@ int run_unipc(SamplerCtx& c, float** result) {
             for (int k = 0; k < K; ++k) u.rho[k] = rhos_c[k];
             u.rho_t = rhos_c[ord - 1]; u.mt = mt;
             float* xo = xin == X ? XN : X;
-            if (!c.count_only && c.ck(launch_unipc(xo, xin, u, c.n, c.s))) return 1;  // corrector (:959-967 / :981-990)
+            if (c.run(launch_unipc, xo, xin, u)) return 1;  // corrector (:959-967 / :981-990)
             *m_out = mt; *x_io = xo;
         } else {
             *x_io = xt;
@@ -653,9 +604,7 @@ int run_unipc(SamplerCtx& c, float** result) {
         gl.back() = G.g[step];
         if (step < steps) ml.back() = m;
     }
-    if (!c.count_only && c.ck(launch_clamp(x, c.n, c.s))) return 1;
-    *result = x;
-    return 0;
+    return c.finish(x, result);
 }
 
 int run_sampler(SamplerCtx& c, float** result) {
@@ -670,7 +619,31 @@ int run_sampler(SamplerCtx& c, float** result) {
         case ADF_SAMPLER_DPM2M: return run_dpm2m(c, result);
         case ADF_SAMPLER_UNIPC: return run_unipc(c, result);
         case ADF_SAMPLER_ADPMPP2S: return run_adpmpp2s(c, result);
-        default: return c.count_only ? 1 : fail(c.h, "unknown sampler kind");
+        default: return c.reject("unknown sampler kind");
+    }
+}
+
+int count_sampler(const adf_sampler_desc* d, const float* sig, int nsig, std::vector<float>* eval_sigmas) {
+    SamplerCtx c{nullptr, nullptr, d, sig, nsig, nullptr, 0};
+    c.count_only = true;
+    c.collect = eval_sigmas;
+    float* r = nullptr;
+    return run_sampler(c, &r) ? -1 : c.nfe;
+}
+
+// one randn_like per step in the reference loops; the device loop reads a draw where the step uses it: the churned steps of EDMSampler
+// (num_steps steps) and DPM2Sampler (num_steps - 1), every step of ADPM2Sampler, the steps of ADPMPP2SSampler whose sigma_next is positive
+int sampler_draws(const adf_sampler_desc& d, const float* sig, int nsig) {
+    switch (d.kind) {
+        case ADF_SAMPLER_EDM: return d.s_churn > 0.f ? d.num_steps : 0;
+        case ADF_SAMPLER_DPM2: return d.s_churn > 0.f ? d.num_steps - 1 : 0;
+        case ADF_SAMPLER_ADPM2: return d.num_steps - 1;
+        case ADF_SAMPLER_ADPMPP2S: {
+            int k = 0;
+            for (int i = 0; i + 1 < d.num_steps && i + 1 < nsig; ++i) k += sig[i + 1] > 0.0f;
+            return k;
+        }
+        default: return 0;
     }
 }
 

@@ -33,6 +33,15 @@ def _require_native() -> bool:
     return os.environ.get("ADF_REQUIRE_NATIVE", "0") not in ("", "0")
 
 
+def conditioning_refusal(net: HipNet, cond_scale: float, kwargs: dict) -> Optional[str]:
+    """The only conditioning keyword the device understands is ``classes`` (labels) on a class-conditional net, where ``cond_scale != 1`` is
+    classifier-free guidance.  Returns None for such a call, otherwise why it leaves the device (``denoise_fn`` and every sampler ask here)."""
+    extra = {k for k, v in kwargs.items() if v is not None}
+    if net.cfg.class_cond:
+        return None if extra == {"classes"} else "a class-conditional net takes exactly the `classes` keyword"
+    return "conditioning keywords / cond_scale != 1 on an unconditional net" if extra or cond_scale != 1.0 else None
+
+
 class Diffusion(nn.Module):
     """What the preconditioned diffusion classes share (diffusion.py:15-97): ``denoise_fn`` with the native fast path and the
     tensor-op compatibility branch, and the training ``forward``.  Subclasses give ``get_scale_weights`` / ``loss_weight`` and the
@@ -54,14 +63,9 @@ class Diffusion(nn.Module):
         return ""
 
     def _native_ok(self, net, inference: bool, cond_scale: float, kwargs: dict) -> bool:
-        """The HIP fast path covers inference (clamp clipping or the dynamic threshold); the only conditioning kwarg it understands is
-        ``classes`` (labels) on a class-conditional net, where ``cond_scale != 1`` is classifier-free guidance."""
-        if not (isinstance(net, HipNet) and inference and 0.0 <= self.dynamic_threshold <= 1.0 and self._precond() is not None):
-            return False
-        extra = {k: v for k, v in kwargs.items() if v is not None}
-        if net.cfg.class_cond:
-            return set(extra) == {"classes"}
-        return not extra and cond_scale == 1.0
+        """The HIP fast path covers inference (clamp clipping or the dynamic threshold) with the conditioning of ``conditioning_refusal``."""
+        return (isinstance(net, HipNet) and inference and 0.0 <= self.dynamic_threshold <= 1.0 and self._precond() is not None
+                and conditioning_refusal(net, cond_scale, kwargs) is None)
 
     def _configure(self, hd) -> None:
         """Preconditioning and clipping of every evaluation the handle runs from here on."""

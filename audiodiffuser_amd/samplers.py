@@ -13,14 +13,14 @@ from __future__ import annotations
 
 import os
 from math import sqrt
-from typing import Callable, Optional
+from typing import Callable, Optional, Tuple
 
 import torch
 import torch.nn as nn
 from torch import Tensor
 
 from . import _lib
-from .diffusion import Diffusion, EluDiffusion
+from .diffusion import Diffusion, EluDiffusion, conditioning_refusal
 from .net import HipNet, UNet1dBase
 
 
@@ -50,12 +50,7 @@ def _native_pair(fn: Callable, net, cond_scale: float, kwargs: dict, noise: Opti
     elif noise is not None and not noise.is_cuda:
         why = "noise is not on a ROCm device"
     else:
-        extra = {k: v for k, v in kwargs.items() if v is not None}
-        if net.cfg.class_cond:
-            if set(extra) != {"classes"}:
-                why = "a class-conditional net takes exactly the `classes` keyword"
-        elif extra or cond_scale != 1.0:
-            why = "conditioning keywords / cond_scale != 1 on an unconditional net"
+        why = conditioning_refusal(net, cond_scale, kwargs)
     if why is None:
         return owner
     if REQUIRE_NATIVE:
@@ -63,17 +58,13 @@ def _native_pair(fn: Callable, net, cond_scale: float, kwargs: dict, noise: Opti
     return None
 
 
-def _condition(net: UNet1dBase, hd, device, cond_scale: float, kwargs: dict, diff: Optional[Diffusion] = None) -> None:
+def _condition(net: UNet1dBase, hd, x: Tensor, cond_scale: float, kwargs: dict, diff: Diffusion) -> None:
     """Labels + guidance scale of this sampler run (the reference forwards them to every fn call, e.g.
     sampler_edm.py:341-345), and the preconditioning and clipping of the owner of ``fn`` (its get_scale_weights; clamp, dynamic
     threshold or -- VDiffusion -- none, diffusion.py:61, :326)."""
-    if diff is not None:
-        diff._configure(hd)
-    else:
-        hd.set_preconditioning()
-        hd.set_dynamic_threshold(0.0)
+    diff._configure(hd)
     if net.cfg.class_cond:
-        hd.set_condition(kwargs["classes"], device, null_labels=False, cond_scale=float(cond_scale))
+        hd.set_condition(kwargs["classes"], x.device, null_labels=False, cond_scale=float(cond_scale))
 
 
 def _draws(x: Tensor, n: int, injected: Optional[Tensor], needed: bool) -> Optional[Tensor]:
@@ -104,7 +95,29 @@ def _prep(noise: Tensor) -> Tensor:
     return noise.detach().to(torch.float32).contiguous()
 
 
-class EDMSampler(nn.Module):
+class _Sampler(nn.Module):
+    """What the ten samplers share: the way into the device loop.  A sampler gives ``_desc`` (its fields of the descriptor), ``cond_scale``
+    and, if its reference loop draws noise, ``_draw_plan``."""
+
+    def _draw_plan(self, sigmas: Tensor) -> Optional[Tuple[int, bool]]:
+        """(number of ``randn_like`` draws the reference loop makes on this schedule, whether the device loop reads them), or None."""
+        return None
+
+    def _native(self, noise: Tensor, fn: Callable, net, sigmas: Tensor, kwargs: dict, injected_noise: Optional[Tensor] = None) -> Optional[Tensor]:
+        """The whole loop as one ``adf_sampler_run``, or None when the call is not native (-> the tensor-op branch).  The order is the
+        reference's: the condition is set before the run, and the draws advance the global generator after everything that can refuse."""
+        diff = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
+        if diff is None:
+            return None
+        x = _prep(noise)
+        hd = net.native(x.device)
+        _condition(net, hd, x, self.cond_scale, kwargs, diff)
+        plan = self._draw_plan(sigmas)
+        inj = _draws(x, plan[0], injected_noise, plan[1]) if plan is not None else None
+        return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, inj).to(noise.dtype)
+
+
+class EDMSampler(_Sampler):
     """EDM stochastic sampler (Heun, optional churn); ``s_churn=0`` is the deterministic Heun ODE solver."""
 
     def __init__(self, s_tmin: float = 0, s_tmax: float = float("inf"), s_churn: float = 150.0, s_noise: float = 1.04,
@@ -114,22 +127,18 @@ class EDMSampler(nn.Module):
         self.num_steps, self.cond_scale, self.use_heun, self.use_graph = num_steps, cond_scale, use_heun, use_graph
 
     def _desc(self, sigma_data: float) -> "_lib.AdfSamplerDesc":
-        d = _lib.AdfSamplerDesc()
-        d.kind, d.num_steps = _lib.SAMPLER_EDM, self.num_steps
-        d.s_tmin, d.s_tmax, d.s_churn, d.s_noise = self.s_tmin, min(self.s_tmax, 3.0e38), self.s_churn, self.s_noise
-        d.use_heun, d.alpha, d.order, d.sigma_data, d.use_graph = int(self.use_heun), 1.0, 0, sigma_data, int(self.use_graph)
-        return d
+        return _lib.make_sampler_desc(_lib.SAMPLER_EDM, self.num_steps, sigma_data, self.use_graph, s_tmin=self.s_tmin, s_tmax=min(self.s_tmax, 3.0e38),
+                                      s_churn=self.s_churn, s_noise=self.s_noise, use_heun=int(self.use_heun))
+
+    def _draw_plan(self, sigmas):
+        return self.num_steps, self.s_churn > 0           # one draw per step, read where gamma > 0 (sampler_edm.py:346)
 
     @torch.no_grad()
     def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, injected_noise: Optional[Tensor] = None,
                 **kwargs) -> Tensor:
-        diff = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
-        if diff is not None:
-            x = _prep(noise)
-            hd = net.native(x.device)
-            _condition(net, hd, x.device, self.cond_scale, kwargs, diff)
-            inj = _draws(x, self.num_steps, injected_noise, self.s_churn > 0)
-            return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, inj).to(noise.dtype)
+        y = self._native(noise, fn, net, sigmas, kwargs, injected_noise)
+        if y is not None:
+            return y
         # ---- interface-compatibility branch (sampler_edm.py:333-397) -----------------------------
         sig = torch.cat([sigmas, torch.zeros_like(sigmas[:1])])
         x = sig[0] * noise
@@ -151,7 +160,7 @@ class EDMSampler(nn.Module):
         return x
 
 
-class EDMAlphaSampler(nn.Module):
+class EDMAlphaSampler(_Sampler):
     """EDM algorithm 3, generalised second-order Runge-Kutta; ``alpha=1`` is Heun."""
 
     def __init__(self, alpha: float = 1.0, num_steps: int = 50, cond_scale: float = 1.0, use_heun: bool = True,
@@ -160,21 +169,13 @@ class EDMAlphaSampler(nn.Module):
         self.alpha, self.num_steps, self.cond_scale, self.use_heun, self.use_graph = alpha, num_steps, cond_scale, use_heun, use_graph
 
     def _desc(self, sigma_data: float) -> "_lib.AdfSamplerDesc":
-        d = _lib.AdfSamplerDesc()
-        d.kind, d.num_steps = _lib.SAMPLER_EDM_ALPHA, self.num_steps
-        d.s_tmin = d.s_tmax = d.s_churn = 0.0
-        d.s_noise = 1.0
-        d.use_heun, d.alpha, d.order, d.sigma_data, d.use_graph = int(self.use_heun), self.alpha, 0, sigma_data, int(self.use_graph)
-        return d
+        return _lib.make_sampler_desc(_lib.SAMPLER_EDM_ALPHA, self.num_steps, sigma_data, self.use_graph, use_heun=int(self.use_heun), alpha=self.alpha)
 
     @torch.no_grad()
     def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, **kwargs) -> Tensor:
-        diff = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
-        if diff is not None:
-            x = _prep(noise)
-            hd = net.native(x.device)
-            _condition(net, hd, x.device, self.cond_scale, kwargs, diff)
-            return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, None).to(noise.dtype)
+        y = self._native(noise, fn, net, sigmas, kwargs)
+        if y is not None:
+            return y
         x = sigmas[0] * noise                                            # sampler_edm.py:284-300
         for i in range(self.num_steps - 1):
             s, s_next = sigmas[i], sigmas[i + 1]
@@ -190,7 +191,7 @@ class EDMAlphaSampler(nn.Module):
         return x
 
 
-class DPMSampler(nn.Module):
+class DPMSampler(_Sampler):
     """DPM-Solver with x0 prediction (sampler_edm.py:495-805): the multistep solver (``multisteps=True``; the shipped
     configuration is configs/experiment/sc09_inference/diffunet_complex_sc09_eval_dpm.yaml:57-64 with
     ``log_time_spacing=False``) and the single-step "DPM-Solver-fast" (``multisteps=False``), each on the sigma grid
@@ -225,25 +226,16 @@ class DPMSampler(nn.Module):
         return self.num_steps if self.multisteps else sum(self.singlestep_orders()[0])
 
     def _desc(self, sigma_data: float) -> "_lib.AdfSamplerDesc":
-        d = _lib.AdfSamplerDesc()
-        d.kind = _lib.SAMPLER_DPM_MULTISTEP if self.multisteps else _lib.SAMPLER_DPM_SINGLESTEP
-        d.num_steps = self.ctor_num_steps
-        d.s_tmin = d.s_tmax = d.s_churn = 0.0
-        d.s_noise = 1.0
-        d.use_heun, d.alpha, d.order, d.sigma_data, d.use_graph = 0, 1.0, int(self.order), sigma_data, int(self.use_graph)
-        d.log_time_spacing = int(bool(self.log_time_spacing))
-        d.eps_pred = int(not self.x0_pred)
-        return d
+        return _lib.make_sampler_desc(_lib.SAMPLER_DPM_MULTISTEP if self.multisteps else _lib.SAMPLER_DPM_SINGLESTEP, self.ctor_num_steps, sigma_data,
+                                      self.use_graph, order=int(self.order), log_time_spacing=int(bool(self.log_time_spacing)),
+                                      eps_pred=int(not self.x0_pred))
 
     @torch.no_grad()
     def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, **kwargs) -> Tensor:
         self._check_supported()
-        diff = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
-        if diff is not None:
-            x = _prep(noise)
-            hd = net.native(x.device)
-            _condition(net, hd, x.device, self.cond_scale, kwargs, diff)
-            return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, None).to(noise.dtype)
+        y = self._native(noise, fn, net, sigmas, kwargs)
+        if y is not None:
+            return y
         # ---- interface-compatibility branch (sampler_edm.py:710-805, :568-690) --------------------
         if not self.x0_pred:
             raise NotImplementedError("DPMSampler(x0_pred=False) with a foreign net / fn: noise prediction runs on the native path only")
@@ -312,7 +304,7 @@ class DPMSampler(nn.Module):
         return x.clamp(-1.0, 1.0)
 
 
-class DPM2MSampler(nn.Module):
+class DPM2MSampler(_Sampler):
     """'DPM-Solver++(2M) Karras' (sampler_edm.py:1056-1131).  The loop reads ``sigmas[i + 1]`` for ``i < num_steps``: the schedule
     must hold ``num_steps + 1`` entries (a final 0 returns the last denoised estimate); with the module's own N-entry schedule the
     reference raises IndexError on its last step, and so does this class.  ``reflow`` is the constructor flag of the class of the same
@@ -324,24 +316,15 @@ class DPM2MSampler(nn.Module):
         self.num_steps, self.cond_scale, self.reflow, self.use_graph = num_steps, cond_scale, reflow, use_graph
 
     def _desc(self, sigma_data: float) -> "_lib.AdfSamplerDesc":
-        d = _lib.AdfSamplerDesc()
-        d.kind, d.num_steps = _lib.SAMPLER_DPM2M, int(self.num_steps)
-        d.s_tmin = d.s_tmax = d.s_churn = 0.0
-        d.s_noise = 1.0
-        d.reflow = int(bool(self.reflow))
-        d.use_heun, d.alpha, d.order, d.sigma_data, d.use_graph = 0, 1.0, 2, sigma_data, int(self.use_graph)
-        return d
+        return _lib.make_sampler_desc(_lib.SAMPLER_DPM2M, self.num_steps, sigma_data, self.use_graph, order=2, reflow=int(bool(self.reflow)))
 
     @torch.no_grad()
     def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, **kwargs) -> Tensor:
         if len(sigmas) < self.num_steps + 1:
             raise IndexError(f"index {self.num_steps} is out of bounds for dimension 0 with size {len(sigmas)}")
-        diff = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
-        if diff is not None:
-            x = _prep(noise)
-            hd = net.native(x.device)
-            _condition(net, hd, x.device, self.cond_scale, kwargs, diff)
-            return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, None).to(noise.dtype)
+        y = self._native(noise, fn, net, sigmas, kwargs)
+        if y is not None:
+            return y
         # ---- interface-compatibility branch --------------------------------------------------------
         x = sigmas[0] * noise
         old = None
@@ -365,7 +348,7 @@ class DPM2MSampler(nn.Module):
         return x.clamp(-1.0, 1.0)
 
 
-class LMSSampler(nn.Module):
+class LMSSampler(_Sampler):
     """'LMS Karras' linear multistep solver (sampler_edm.py:1134-1190): ``num_steps - 1`` evaluations, the last ``order``
     derivatives combined with the integrals of their Lagrange basis polynomials over the step (the reference integrates
     them with scipy ``quad`` on fp32 NumPy scalars, so its values carry ~1e-7 relative noise that depends on the NumPy
@@ -390,23 +373,15 @@ class LMSSampler(nn.Module):
         return acc * half
 
     def _desc(self, sigma_data: float) -> "_lib.AdfSamplerDesc":
-        d = _lib.AdfSamplerDesc()
-        d.kind, d.num_steps = _lib.SAMPLER_LMS, int(self.num_steps)
-        d.s_tmin = d.s_tmax = d.s_churn = 0.0
-        d.s_noise = 1.0
-        d.use_heun, d.alpha, d.order, d.sigma_data, d.use_graph = 0, 1.0, int(self.order), sigma_data, int(self.use_graph)
-        return d
+        return _lib.make_sampler_desc(_lib.SAMPLER_LMS, self.num_steps, sigma_data, self.use_graph, order=int(self.order))
 
     @torch.no_grad()
     def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, **kwargs) -> Tensor:
         if not 1 <= self.order <= 4:
             raise ValueError("LMSSampler: order must be 1..4")
-        diff = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
-        if diff is not None:
-            x = _prep(noise)
-            hd = net.native(x.device)
-            _condition(net, hd, x.device, self.cond_scale, kwargs, diff)
-            return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, None).to(noise.dtype)
+        y = self._native(noise, fn, net, sigmas, kwargs)
+        if y is not None:
+            return y
         # ---- interface-compatibility branch --------------------------------------------------------
         t = sigmas.detach().cpu().numpy()
         x = sigmas[0] * noise
@@ -420,7 +395,7 @@ class LMSSampler(nn.Module):
         return x.clamp(-1.0, 1.0)
 
 
-class DPM2Sampler(nn.Module):
+class DPM2Sampler(_Sampler):
     """'DPM2 Karras' (reference: src/models/components/sampler_edm.py:401-493): midpoint method in log-sigma with the
     EDM churn.  ``injected_noise`` ([num_steps-1, B, C, L]) replaces the per-step ``randn_like`` draws."""
 
@@ -431,23 +406,18 @@ class DPM2Sampler(nn.Module):
         self.s_tmin, self.s_tmax, self.s_noise, self.s_churn, self.use_graph = s_tmin, s_tmax, s_noise, s_churn, use_graph
 
     def _desc(self, sigma_data: float) -> "_lib.AdfSamplerDesc":
-        d = _lib.AdfSamplerDesc()
-        d.kind, d.num_steps = _lib.SAMPLER_DPM2, self.num_steps
-        d.s_tmin, d.s_tmax, d.s_churn, d.s_noise = self.s_tmin, min(self.s_tmax, 3.0e38), self.s_churn, self.s_noise
-        d.use_heun, d.alpha, d.order, d.sigma_data, d.use_graph = 0, 1.0, 0, sigma_data, int(self.use_graph)
-        d.rho, d.eta = float(self.rho), 1.0
-        return d
+        return _lib.make_sampler_desc(_lib.SAMPLER_DPM2, self.num_steps, sigma_data, self.use_graph, s_tmin=self.s_tmin, s_tmax=min(self.s_tmax, 3.0e38),
+                                      s_churn=self.s_churn, s_noise=self.s_noise, rho=float(self.rho), eta=1.0)
+
+    def _draw_plan(self, sigmas):
+        return self.num_steps - 1, self.s_churn > 0       # one draw per step, read where gamma > 0 (sampler_edm.py:439)
 
     @torch.no_grad()
     def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, injected_noise: Optional[Tensor] = None,
                 **kwargs) -> Tensor:
-        diff = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
-        if diff is not None:
-            x = _prep(noise)
-            hd = net.native(x.device)
-            _condition(net, hd, x.device, self.cond_scale, kwargs, diff)
-            inj = _draws(x, self.num_steps - 1, injected_noise, self.s_churn > 0)
-            return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, inj).to(noise.dtype)
+        y = self._native(noise, fn, net, sigmas, kwargs, injected_noise)
+        if y is not None:
+            return y
         # ---- interface-compatibility branch (sampler_edm.py:428-493) ----------------------------------
         x = sigmas[0] * noise
         gam = torch.where((sigmas >= self.s_tmin) & (sigmas <= self.s_tmax), min(self.s_churn / self.num_steps, sqrt(2) - 1), 0.0)
@@ -467,7 +437,7 @@ class DPM2Sampler(nn.Module):
         return x.clamp(-1.0, 1.0)
 
 
-class ADPM2Sampler(nn.Module):
+class ADPM2Sampler(_Sampler):
     """'DPM2 a Karras', the ancestral DPM-Solver-2 (reference: src/models/components/stochastic_sampler_edm.py:35-100;
     the Lightning module's default sampler).  Fresh noise of scale sigma_up is added every step:
     ``injected_noise`` ([num_steps-1, B, C, L]) replaces those ``randn_like`` draws."""
@@ -477,23 +447,17 @@ class ADPM2Sampler(nn.Module):
         self.rho, self.num_steps, self.cond_scale, self.eta, self.use_graph = rho, num_steps, cond_scale, eta, use_graph
 
     def _desc(self, sigma_data: float) -> "_lib.AdfSamplerDesc":
-        d = _lib.AdfSamplerDesc()
-        d.kind, d.num_steps = _lib.SAMPLER_ADPM2, self.num_steps
-        d.s_tmin, d.s_tmax, d.s_churn, d.s_noise = 0.0, 3.0e38, 0.0, 1.0
-        d.use_heun, d.alpha, d.order, d.sigma_data, d.use_graph = 0, 1.0, 0, sigma_data, int(self.use_graph)
-        d.rho, d.eta = float(self.rho), float(self.eta)
-        return d
+        return _lib.make_sampler_desc(_lib.SAMPLER_ADPM2, self.num_steps, sigma_data, self.use_graph, s_tmax=3.0e38, rho=float(self.rho), eta=float(self.eta))
+
+    def _draw_plan(self, sigmas):
+        return self.num_steps - 1, True                   # one draw per step (stochastic_sampler_edm.py:82)
 
     @torch.no_grad()
     def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, injected_noise: Optional[Tensor] = None,
                 **kwargs) -> Tensor:
-        diff = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
-        if diff is not None:
-            x = _prep(noise)
-            hd = net.native(x.device)
-            _condition(net, hd, x.device, self.cond_scale, kwargs, diff)
-            inj = _draws(x, self.num_steps - 1, injected_noise, True)                          # reference draw order (:82)
-            return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, inj).to(noise.dtype)
+        y = self._native(noise, fn, net, sigmas, kwargs, injected_noise)
+        if y is not None:
+            return y
         # ---- interface-compatibility branch (stochastic_sampler_edm.py:29-32, :53-100) -----------------
         x = sigmas[0] * noise
         for i in range(self.num_steps - 1):
@@ -509,7 +473,7 @@ class ADPM2Sampler(nn.Module):
         return x.clamp(-1.0, 1.0)
 
 
-class ADPMPP2SSampler(nn.Module):
+class ADPMPP2SSampler(_Sampler):
     """'DPM++ 2S a Karras', ancestral DPM-Solver++(2S) (reference: src/models/components/stochastic_sampler_edm.py:102-178):
     ``num_steps - 1`` steps of two evaluations (one when sigma_down is 0), fresh noise of scale sigma_up after every step whose
     sigma_next is positive -- ``injected_noise`` ([that many, B, C, L]) replaces those ``randn_like`` draws.  ``rho`` is accepted and,
@@ -520,24 +484,18 @@ class ADPMPP2SSampler(nn.Module):
         self.rho, self.num_steps, self.cond_scale, self.eta, self.use_graph = rho, num_steps, cond_scale, eta, use_graph
 
     def _desc(self, sigma_data: float) -> "_lib.AdfSamplerDesc":
-        d = _lib.AdfSamplerDesc()
-        d.kind, d.num_steps = _lib.SAMPLER_ADPMPP2S, self.num_steps
-        d.s_tmin, d.s_tmax, d.s_churn, d.s_noise = 0.0, 3.0e38, 0.0, 1.0
-        d.use_heun, d.alpha, d.order, d.sigma_data, d.use_graph = 0, 1.0, 0, sigma_data, int(self.use_graph)
-        d.rho, d.eta = float(self.rho), float(self.eta)
-        return d
+        return _lib.make_sampler_desc(_lib.SAMPLER_ADPMPP2S, self.num_steps, sigma_data, self.use_graph, s_tmax=3.0e38, rho=float(self.rho),
+                                      eta=float(self.eta))
+
+    def _draw_plan(self, sigmas):
+        return int((sigmas[1:self.num_steps].detach().cpu() > 0).sum()), True      # one draw per step with sigma_next > 0 (:158)
 
     @torch.no_grad()
     def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, injected_noise: Optional[Tensor] = None,
                 **kwargs) -> Tensor:
-        diff = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
-        if diff is not None:
-            x = _prep(noise)
-            hd = net.native(x.device)
-            _condition(net, hd, x.device, self.cond_scale, kwargs, diff)
-            n_draws = int((sigmas[1:self.num_steps].detach().cpu() > 0).sum())                 # one per step with sigma_next > 0 (:158)
-            inj = _draws(x, n_draws, injected_noise, True)
-            return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, inj).to(noise.dtype)
+        y = self._native(noise, fn, net, sigmas, kwargs, injected_noise)
+        if y is not None:
+            return y
         # ---- interface-compatibility branch (stochastic_sampler_edm.py:29-32, :117-178) ----------------
         x = sigmas[0] * noise
         k = 0
@@ -561,7 +519,7 @@ class ADPMPP2SSampler(nn.Module):
         return x.clamp(-1.0, 1.0)
 
 
-class UniPCSampler(nn.Module):
+class UniPCSampler(_Sampler):
     """Uni-PC (sampler_edm.py:807-1053, variant 'bh2'): multistep predictor-corrector, NFE = its step count -- ``num_steps`` on a lambda
     grid linear between the first and the last sigma (``log_time_spacing``, the default) or ``num_steps - 1`` on the sigma list itself.
     The reference only runs on 4-D states (hard-coded ``einsum('k,bkchw->bchw')``); here any state shape works."""
@@ -575,23 +533,15 @@ class UniPCSampler(nn.Module):
         self.use_graph = use_graph
 
     def _desc(self, sigma_data: float) -> "_lib.AdfSamplerDesc":
-        d = _lib.AdfSamplerDesc()
-        d.kind, d.num_steps = _lib.SAMPLER_UNIPC, int(self._ctor_steps)
-        d.s_tmin = d.s_tmax = d.s_churn = 0.0
-        d.s_noise = 1.0
-        d.use_heun, d.alpha, d.order, d.sigma_data, d.use_graph = 0, 1.0, int(self.order), sigma_data, int(self.use_graph)
-        d.log_time_spacing, d.eps_pred = int(self.log_time_spacing), int(not self.x0_pred)
-        return d
+        return _lib.make_sampler_desc(_lib.SAMPLER_UNIPC, self._ctor_steps, sigma_data, self.use_graph, order=int(self.order),
+                                      log_time_spacing=int(self.log_time_spacing), eps_pred=int(not self.x0_pred))
 
     @torch.no_grad()
     def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, **kwargs) -> Tensor:
         assert self.num_steps >= self.order                                        # :1001
-        diff = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
-        if diff is not None:
-            x = _prep(noise)
-            hd = net.native(x.device)
-            _condition(net, hd, x.device, self.cond_scale, kwargs, diff)
-            return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, None).to(noise.dtype)
+        y = self._native(noise, fn, net, sigmas, kwargs)
+        if y is not None:
+            return y
         # ---- interface-compatibility branch (same recurrences as tensor ops around a foreign fn / net) ----------------------------
         steps, order = self.num_steps, self.order
         if self.log_time_spacing:
