@@ -54,15 +54,32 @@ class UNetModel(HipNet):
                              conv_resample=conv_resample, num_classes=num_classes, num_heads=num_heads, num_head_channels=num_head_channels,
                              use_scale_shift_norm=use_scale_shift_norm, resblock_updown=resblock_updown,
                              use_new_attention_order=use_new_attention_order)
+        st = structure(self.cfg)
         if compute_dtype in ("bf16", "bfloat16"):
             # the bf16 (MFMA) conv routes read K in 64-channel chunks from either source of a skip concat: say which layer breaks that HERE,
             # not as a generic "input channels must be a multiple of the 128-byte K chunk" at the first forward (WaveNetNoise does the same)
-            st = structure(self.cfg)
             for layers in st.input_blocks[1:] + [st.middle] + st.output_blocks:
                 for l in layers:
                     if l.cin % 64 or l.cout % 64:
                         raise ValueError(f"compute_dtype='bf16' needs every conv width to be a multiple of 64 channels: {l.pre} is "
                                          f"{l.cin} -> {l.cout} (model_channels={model_channels}, channel_mult={tuple(channel_mult)}); use compute_dtype='fp32'")
+        # what the device path cannot serve is refused HERE, with the layer, not by the library at the first forward: adf_adm_create takes
+        # model_channels up to 256, a conv reads at most 1024 input channels (both halves of a skip concat), the attention kernels are built for
+        # head dims 8 / 16 / 32 / 64.  A model_channels that is no multiple of 32 is NOT refused here although adf_adm_create refuses it: the plugin
+        # contract (tests/test_adm.py) is that such an fp32 net constructs, for its state_dict layout without a device -- and with its heads undefined
+        # for the device, the head-dim rule is applied to the widths the library takes only
+        if model_channels > 256:
+            raise ValueError(f"the HIP UNetModel serves model_channels up to 256, not {model_channels}")
+        for layers in st.input_blocks[1:] + [st.middle] + st.output_blocks:
+            for l in layers:
+                if l.cin > 1024:
+                    raise ValueError(f"the HIP UNetModel serves convs of at most 1024 input channels: {l.pre} reads {l.cin} "
+                                     f"(model_channels={model_channels}, channel_mult={tuple(channel_mult)})")
+                if l.kind == "attn" and model_channels % 32 == 0:
+                    nh = self.cfg.heads(l.cin)
+                    if nh < 1 or l.cin % nh or l.cin // nh not in (8, 16, 32, 64):
+                        raise ValueError(f"the HIP UNetModel's attention needs a head dim of 8, 16, 32 or 64: {l.pre} has {l.cin} channels in {nh} heads "
+                                         f"(num_heads={num_heads}, num_head_channels={num_head_channels})")
         for name, (shape, kind) in param_specs(self.cfg).items():
             self._register(name, nn.Parameter(_init_like_reference(name, shape, kind)))
 

@@ -47,7 +47,9 @@ int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out) {
     p->coef = (float*)dalloc(h, (size_t)B * 4 * 4, p);
     bool ok = p->arena && p->stats && p->temb && p->film && p->coef;
     for (int i = 0; i < 10; ++i) { p->sb[i] = (float*)dalloc(h, wave * 4, p); ok = ok && p->sb[i]; }
-    p->noise_stage = (float*)dalloc(h, wave * 4, p);
+    // noise_stage serves as the sampler's noise ([B][out_channels][L]) AND as the network input of the warm-up below ([B][in_channels][L]): the larger
+    const size_t wave_in = (size_t)B * std::max(c.in_channels, c.out_channels) * L;
+    p->noise_stage = (float*)dalloc(h, wave_in * 4, p);
     p->out_stage = (float*)dalloc(h, wave * 4, p);
     ok = ok && p->noise_stage && p->out_stage;
     if (!ok) { destroy_plan(h, p); return fail(h, "device allocation failed for the workspace"); }

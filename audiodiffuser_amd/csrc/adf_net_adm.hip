@@ -111,8 +111,10 @@ int AdmNet::build_weights(adf_handle* h) {
         for (const AdmRes& r : a.res) { g = gcd(g, r.cin / 32); g = gcd(g, r.cout / 32); }
         for (const AdmAttn& t : a.attn) g = gcd(g, t.c / 32);
         for (int sc : a.skip_ch) g = gcd(g, sc);       // a concat splits at the skip's width
-        a.fg = g < 1 ? 1 : (g > 4 ? 4 : g);
-        while (128 % a.fg) --a.fg;
+        // the largest power of two dividing g, at most 4: it must divide every group size (g) AND the 128-channel tile of the conv epilogue's
+        // statistics (clamping g to 4 and stepping down to a divisor of 128 gave 2 for g = 3 and 4 for g = 5, 6, 7: widths 96, 160, 192, 224)
+        a.fg = 1;
+        while (a.fg < 4 && g > 0 && g % (2 * a.fg) == 0) a.fg *= 2;
     }
     // pass 2: registry, in the module's registration order
     Registrar R{h};

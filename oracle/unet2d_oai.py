@@ -101,13 +101,14 @@ def res_block(p: P, l: _Layer, x: torch.Tensor, emb: torch.Tensor, scale_shift: 
         else:
             h = F.avg_pool2d(h, 2, 2)
             x = F.avg_pool2d(x, 2, 2)
-    h = rec(".h1", conv2d(p, f"{pre}.in_layers.2", h))
+    h = conv2d(p, f"{pre}.in_layers.2", h)
     e = F.linear(F.silu(emb), p[f"{pre}.emb_layers.1.weight"], p[f"{pre}.emb_layers.1.bias"])[:, :, None, None]
     if scale_shift:                        # :262-267
+        h = rec(".h1", h)
         scale, shift = torch.chunk(e, 2, dim=1)
         h = group_norm32(p, f"{pre}.out_layers.0", h) * (1 + scale) + shift
-    else:                                  # :268-270
-        h = group_norm32(p, f"{pre}.out_layers.0", h + e)
+    else:                                  # :268-270; ".h1" is what the device stores, conv1 + emb_out (as in the bf16 branch above)
+        h = group_norm32(p, f"{pre}.out_layers.0", rec(".h1", h + e))
     h = conv2d(p, f"{pre}.out_layers.3", F.silu(h))       # dropout is the identity at inference
     skip = rec(".skip", conv2d(p, f"{pre}.skip_connection", x)) if l.cin != l.cout else x
     return skip + h

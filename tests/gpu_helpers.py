@@ -2,6 +2,8 @@
 and compare every recorded activation ("tap") with the CPU oracle on the same inputs."""
 from __future__ import annotations
 
+import re
+
 import torch
 
 import audiodiffuser_amd as A
@@ -75,3 +77,19 @@ def tap_errors(cfg, x, t, dtype="fp32", flags=0):
         errs[name] = rel_err(got, taps_o[name])
     errs["out"] = rel_err(y.cpu(), y_o)
     return errs, y.cpu(), y_o
+
+
+_C2_LINE = re.compile(r"^\[adf conv2d\] (\S+)\s+B=(\d+) H=(\d+) W=(\d+) cin=(\d+) c0=(\d+) cout=(\d+) taps=(\d+) mode=(\d+) ab=(\d+) act=(\d+) res=(\d+) stats=(\d+)$")
+_C2_KEYS = ("B", "H", "W", "cin", "c0", "cout", "taps", "mode", "ab", "act", "res", "stats")
+
+
+def conv2d_trace_lines(stderr: str):
+    """The ``[adf conv2d]`` lines a process started with ADF_C2_TRACE=1 wrote (one per launch_conv2d call), as dicts: "route" plus the integers of
+    the line.  A line of that prefix that does not parse is an error, so a change of the trace format cannot silently empty a route census."""
+    lines = []
+    for l in stderr.splitlines():
+        if l.startswith("[adf conv2d]"):
+            m = _C2_LINE.match(l.strip())
+            assert m, f"unparsed route line: {l!r}"
+            lines.append(dict(zip(_C2_KEYS, map(int, m.groups()[1:])), route=m.group(1)))
+    return lines

@@ -5,7 +5,8 @@ pixel counts are multiples of 256).  The cases below reach what that point never
 convs, fine-statistics groups of 1 and 2 channels, widths 160 / 192 / 320 / 384 / 512 and the 1024-channel concat, head dims 32 and 64 from the
 2-D walker, head dim 128 at token counts off the 32-key tile, feed-forward widths 384 / 640 / 768 / 1024, global-context pooling over 1 to 1584
 rows, the unscaled skip concat, two transformer layers per block, no middle attention, no final resnet block, one to four cross-embed kernels,
-batches of 3, 5 and 7 with per-sample times and labels.
+batches of 3, 5 and 7 with per-sample times and labels, and (fg2_b128: fg2's structure at B = 128, 32 x 32) the 128-pixel gather route of launch_conv2d,
+which needs 512 tiles (fp32 oracle against float64 there: ups.0.0.h1 3.8e-6).
 
 Every case compares the output AND every tensor the device walker records (``hd.tap_names()``, unsubsampled) with oracle/unet2d.py run in
 float64 (``fine_taps``).  Bar per tensor: FP32_TIGHT = 5e-5 of max |reference| (the project's exact-fp32 bar), or 4 x the tensor's own
@@ -17,7 +18,7 @@ Measured on one MI355X, worst device-vs-float64 tensor per case (and the output)
   fg1        downs.1.1.h1   3.1e-6   (out 1.8e-6)        sc09_wide   ups.2.1.1.h1    3.3e-6   (out 2.0e-6)
   fg2        ups.0.1.0.h1   3.9e-6   (out 2.6e-6)        sc09_cls7   ups.2.1.1.h1    3.6e-6   (out 2.3e-6)
   sc09_odd   ups.2.1.1.h1   3.7e-6   (out 2.1e-6)        sc09_cls7, labels dropped   ups.1.0.h1  3.4e-6   (out 2.0e-6)
-  sc09_min   ups.2.1.1.h1   2.9e-6   (out 2.1e-6)
+  sc09_min   ups.2.1.1.h1   2.9e-6   (out 2.1e-6)        fg2_b128    ups.0.0.h1      4.8e-6   (out 2.2e-6)
 One handle through four shapes: at most 3.4e-6.  Denoiser epilogue on wide3: EluDiffusion 1.7e-6, VDiffusion(for_edm) 1.3e-6.  fg1 sample 3 alone
 against its row of the batch of 5: 2.7e-6 at worst (ups.0.1.1.h2), output 1.7e-6.  No case exposed a kernel defect.
 
@@ -29,13 +30,20 @@ That the sweep has teeth was checked once on four value-only edits of adf_unet2d
                                                                has (one wave holds a row), so the guard is redundant and the edit changes no value
 """
 import functools
+import json
+import os
+import subprocess
+import sys
 
 import pytest
 import torch
 
 import audiodiffuser_amd as A
+from gpu_helpers import conv2d_trace_lines
 from oracle import unet2d as U
 import precond_ref as PR
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 FP32_TIGHT = 5e-5            # tests/test_unet2d_gpu.py
 
@@ -67,6 +75,9 @@ CASES = {
     "sc09_wide": (U.config_sc09(0), (1, 16, 208), 24),
     "sc09_cls7": (U.config_sc09(10), (7, 32, 48), 25),
 }
+# fg2's structure at the smallest batch x image whose first level (16 x 16, 192 channels: ny = 2) fills launch_conv2d's 128-pixel gather route:
+# B*H*W/4 / 128 * 2 = 512 tiles (see test_large_batch_takes_the_128_pixel_gather_kernel)
+CASES["fg2_b128"] = (CASES["fg2"][0], (128, 32, 32), 23)
 
 
 def inputs(cfg, shape, seed=0):
@@ -179,6 +190,30 @@ def test_every_layer_vs_float64_oracle(cid):
     run_and_compare(net, cfg, w, w64, x, t, cl, 0.0, cid)
     if cid == "sc09_cls7":
         run_and_compare(net, cfg, w, w64, x, t, cl, 1.0, cid + " labels dropped")
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_large_batch_takes_the_128_pixel_gather_kernel():
+    """fg2_b128 (B = 128 at 32 x 32) is the one case of this module whose convs reach launch_conv2d's route g128 (conv2d_gemm_kernel<float, 128>: H*W % 128
+    == 0 and B*H*W/128 * ceil(cout/128) >= 512), the route of the benchmarked 64 x 2 x 256 x 128 workload; every other case stays far below 512 tiles.  Its
+    values are held to the float64 oracle by test_every_layer_vs_float64_oracle[fg2_b128]; here a child process with ADF_C2_TRACE=1 proves the route.  At the
+    first level (16 x 16 pixels, 192 channels, W no multiple of 32, so the 3x3 convs take the gather kernel too): 128 * 256 / 128 = 256 pixel tiles x ny = 2
+    = 512 for the stride-2 conv (Downsample), the 3x3 convs and res_conv (1x1 over the concat), x ny = 6 = 1536 for PixelShuffleUpsample's linear."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "diag", "gpu_conv2d_routes_report.py"), "u2d_fg2_b128"], capture_output=True, text=True,
+                       env=dict(os.environ, ADF_C2_TRACE="1"), timeout=240)
+    assert r.returncode == 0, r.stderr[-3000:]
+    rep = json.loads(r.stdout.strip().splitlines()[-1])
+    assert rep["finite"] and rep["shape"] == list(CASES["fg2_b128"][1])
+    rows = conv2d_trace_lines(r.stderr)
+    assert rows and all(q["B"] == 128 for q in rows)
+    lv0 = [q for q in rows if (q["H"], q["W"]) == (16, 16)]
+    assert len(lv0) >= 12 and all(q["route"] == "g128" and 128 * 256 // 128 * -(-q["cout"] // 128) >= 512 for q in lv0), lv0
+    assert any(q["mode"] == 2 and q["cout"] == 192 for q in lv0)                           # Downsample: stride 2, two N tiles (the second partial), 512 tiles
+    assert any(q["taps"] == 1 and q["cout"] == 192 and q["c0"] < q["cin"] for q in lv0)    # res_conv over the concat: 1x1, split source
+    assert any(q["taps"] == 1 and q["cout"] == 768 for q in lv0)                           # PixelShuffleUpsample's linear: six N tiles
+    assert any(q["taps"] == 9 and q["mode"] == 0 and q["ab"] and q["res"] for q in lv0)    # block2 with the GroupNorm prologue and the residual
+    assert all(q["route"] != "g128" for q in rows if (q["H"], q["W"]) == (8, 8))           # the second level (64 pixels per image) stays on the 64-pixel kernel
 
 
 @pytest.mark.gpu
