@@ -71,6 +71,53 @@ class UNet1dConfig:
         if self.class_cond and not (isinstance(self.num_classes, int) and self.num_classes > 0):
             raise ValueError("class_cond=True needs num_classes (label conditioning; class_embed_dim inputs are outside the path)")
 
+    def validate_device(self, compute_dtype: str = "fp32") -> None:
+        """What the reference constructs and the HIP library cannot serve, refused here with the layer named -- the library would refuse
+        it (or fail a launch) at the first forward.  ``compute_dtype``: bf16 stores rows in 16-byte chunks of 8 channels, fp32 and f32x3 of 4."""
+        self.validate()
+        epc = 8 if compute_dtype == "bf16" else 4
+        ch, n, g = self.channels, self.num_layers, self.resnet_groups
+        if self.window_length > 16:
+            raise ValueError(f"unet.to_out: window_length up to 16 is served, got {self.window_length}")
+        if not self.use_nearest_upsample:
+            for u, i in enumerate(reversed(range(n))):
+                if self.factors[i] < 2:
+                    raise NotImplementedError(f"unet.upsamples.{u}.upsample (and unet.downsamples.{i}.downsample): a factor of 1 is a plain Conv1d(k = 3) "
+                                              "in the reference (unet1d.py:231-234), which is not built; factors start at 2")
+        if g > 256:
+            raise ValueError(f"unet.downsamples.0: resnet_groups up to 256 are served (GroupNorm statistics), got {g}")
+        widths = [("unet.to_in", self.num_filters, False)]
+        for i in range(n):
+            widths.append((f"unet.downsamples.{i}", ch * self.multipliers[i + 1], True))
+        for name, c, normed in widths:
+            if c < 1 or c % epc:
+                raise ValueError(f"{name}: {c} channels; {compute_dtype} rows are stored in chunks of {epc} channels, so every width must be a multiple of {epc}")
+            if c // epc > 256:
+                raise ValueError(f"{name}: {c} channels are more than the 256 chunks of {epc} channels a {compute_dtype} row may have")
+            if normed and (g < 1 or c % g):
+                raise ValueError(f"{name}: resnet_groups = {g} does not divide its {c} channels (GroupNorm)")
+        heads = self.attention_heads
+        att = [(f"unet.downsamples.{i}.transformer", ch * self.multipliers[i + 1]) for i in range(n) if self.attentions[i]]
+        if self.use_attention_bottleneck:
+            att.append(("unet.bottleneck.transformer", ch * self.multipliers[-1]))
+        for name, c in att:
+            if heads < 1 or c % heads or c // heads not in (8, 16, 32, 64):
+                raise ValueError(f"{name}: the attention kernels serve a head dim of 8, 16, 32 or 64; {c} channels in {heads} heads")
+            mid = int(c * self.attention_multiplier)
+            if mid < 1 or mid % epc or mid // epc > 256:
+                raise ValueError(f"{name}.feed_forward: {mid} channels (attention_multiplier = {self.attention_multiplier}) must be a multiple of {epc} "
+                                 f"and at most {256 * epc} ({compute_dtype})")
+        # the two checks below restate launch_to_in / launch_to_out (csrc/adf_kernels.hip): their LDS sizes and the gates of their MFMA / row forms; keep
+        # them in step with the launchers (the row form of to_in also needs L % 4 == 0, which every total downsample of 4 or more gives)
+        nf, wl = self.num_filters, self.window_length
+        fast_in = self.in_channels == 1 and wl == 8 and self.stride == 2 and (nf // epc) & (nf // epc - 1) == 0
+        if not fast_in and nf * self.in_channels * wl * 4 > 60000:
+            raise ValueError(f"unet.to_in: num_filters * in_channels * window_length = {nf * self.in_channels * wl} weights do not fit the kernel's 60000-byte tile")
+        mfma_out = nf <= 128 and ((compute_dtype == "bf16" and nf % 16 == 0) or (compute_dtype == "f32x3" and nf % 64 == 0))
+        halo = -(-wl // max(self.stride, 1))
+        if not mfma_out and (nf * wl + (256 + 2 * halo) * wl) * 4 > 65536:
+            raise ValueError(f"unet.to_out: num_filters * window_length = {nf * wl} weights and the tap products do not fit 64 KiB of LDS")
+
     def to_kwargs(self) -> dict:
         """kwargs accepted by the reference ``UNet1dBase`` constructor."""
         d = asdict(self)

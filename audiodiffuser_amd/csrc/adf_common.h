@@ -208,6 +208,44 @@ __device__ __forceinline__ void gn_affine(const GnFinalizeArgs& a, int b, int c,
     gn_affine_finish<FAST>(a, c, gn_affine_load(a, b, c), A, Bc);
 }
 
+// A GroupNorm group that lies across the end of source 0 and the start of source 1: an odd group count over two equal sources (one group per
+// sample, resnet_groups = 1, is the common case).  gn_affine_load above reads one source per group, so the launchers that meet such a group take
+// the two functions below (gn_finalize_kernel, gn_norm_apply_kernel); the GEMM kernels that derive their table themselves decline the shape.
+__device__ __forceinline__ bool gn_group_straddles(const GnFinalizeArgs& a, int c) {
+    const int gs = (a.c0 + a.c1) / a.G, cstart = (c / gs) * gs;
+    return cstart < a.c0 && cstart + gs > a.c0;
+}
+// sum and sum of squares of [src0 ; scale1 * src1] over the straddling group that starts at channel cstart (the launchers check c0 == c1, so the
+// group is a whole number of stored groups of either source)
+__device__ __forceinline__ void gn_straddle_sums(const GnFinalizeArgs& a, int b, int cstart, int gs, double& sum, double& sq) {
+    const int fg0 = a.c0 / a.G, fg1 = a.c1 / a.G;
+    const double sc = (double)a.scale1;
+    sum = 0.0; sq = 0.0;
+    for (int g = cstart / fg0; g < a.G; ++g) { sum += a.stats0[((size_t)b * a.G + g) * 2]; sq += a.stats0[((size_t)b * a.G + g) * 2 + 1]; }
+    for (int g = 0; g < (cstart + gs - a.c0) / fg1; ++g) {
+        sum += sc * a.stats1[((size_t)b * a.G + g) * 2];
+        sq += sc * sc * a.stats1[((size_t)b * a.G + g) * 2 + 1];
+    }
+}
+__device__ __forceinline__ void gn_affine_straddle(const GnFinalizeArgs& a, int b, int c, float& A, float& Bc) {
+    const int ctot = a.c0 + a.c1, gs = ctot / a.G;
+    double sum, sq;
+    gn_straddle_sums(a, b, (c / gs) * gs, gs, sum, sq);
+    const double cnt = (double)a.L * (double)gs;
+    const double mean = sum / cnt;
+    double var = sq / cnt - mean * mean;
+    var = var > 0.0 ? var : 0.0;
+    A = (float)(1.0 / sqrt(var + (double)a.eps)) * a.gamma[c];
+    Bc = a.beta[c] - (float)mean * A;
+    if (a.film) {
+        float fs = a.film[(size_t)b * a.film_bstride + c] + 1.0f, fh = a.film[(size_t)b * a.film_bstride + ctot + c];
+        if (a.film2) { fs += a.film2[(size_t)b * a.film2_bstride + c]; fh += a.film2[(size_t)b * a.film2_bstride + ctot + c]; }
+        A *= fs;
+        Bc = fmaf(Bc, fs, fh);
+    }
+    if (c >= a.c0) A *= a.scale1;
+}
+
 // SiLU = v * sigmoid(v) with the hardware exp2 / rcp (each ~1 ulp): 5 VALU ops, 2 of them transcendental
 __device__ __forceinline__ float silu_f(float v) {
     return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f));

@@ -467,7 +467,10 @@ const char* launch_conv_gemm(const GemmArgs& a_in, int dtype, hipStream_t stream
     if (gn_in_kernel < 0) gn_in_kernel = (int)adf_tuning("ADF_GEMM_GN", 1);
     auto settle_gn = [&](bool in_kernel) -> const char* {
         if (!gn_pending) return nullptr;
-        in_kernel = in_kernel && gn_in_kernel;
+        // (a GroupNorm group across the two sources -- an odd group count -- is derived by gn_finalize alone: adf_common.h gn_group_straddles)
+        const GnFinalizeArgs& gn = a.seg[0].gn;
+        const int gn_gs = gn.G > 0 ? (gn.c0 + gn.c1) / gn.G : 0;
+        in_kernel = in_kernel && gn_in_kernel && gn_gs > 0 && gn.c0 % gn_gs == 0;
         const char* err = nullptr;
         if (!in_kernel) {
             if (!a.gn_ready) err = launch_gn_finalize(a.seg[0].gn, stream);

@@ -283,7 +283,7 @@ class UNet1dBase(HipNet):
         self.cfg = UNet1dConfig(channels=channels, cond_drop_prob=cond_drop_prob, class_cond=bool(class_cond),
                                 num_classes=num_classes if class_cond else None, **kwargs)
         self.cfg.out_channels = out_channels if out_channels is not None else self.cfg.in_channels  # unet1d.py:607
-        self.cfg.validate()
+        self.cfg.validate_device(compute_dtype)        # refuses, with the layer named, what the library would refuse at the first forward
         self._specs = param_specs(self.cfg)
         for name, (shape, kind) in self._specs.items():
             self._register(name, nn.Parameter(_init_like_reference(name, shape, kind)))

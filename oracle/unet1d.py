@@ -23,6 +23,9 @@ bf16 roundings that flip because of it), so the GPU tests can hold the bf16 kern
 tighter than bf16-vs-fp32.  ``force`` ("teacher forcing"): a mapping tap-name -> tensor; each recorded
 activation is compared with the forced value (error into ``errs``) and REPLACED by it, so every layer is
 checked in isolation on exactly the inputs the device layer saw.
+
+Float64 run (opt-in, ``storage="fp32"`` only): pass float64 weights, ``x`` and ``t`` and every operation, the attention softmax included, runs in
+float64 -- the reference that tests/test_unet1d_sweep_gpu.py holds the fp32 kernels to.  On float32 inputs nothing changes.
 """
 from __future__ import annotations
 
@@ -158,7 +161,7 @@ def self_attention(p: P, pre: str, x: torch.Tensor, heads: int, q: Storage = FP3
         pv = q.r(pr) if mfma_attention(d, n) else pr
         o = torch.matmul(pv, v) / pr.sum(dim=-1, keepdim=True)
     else:
-        attn = sim.softmax(dim=-1, dtype=torch.float32)
+        attn = sim.softmax(dim=-1, dtype=sim.dtype)       # the reference asks for float32 (attention_utils.py:172); float64 in the float64 run
         o = torch.matmul(attn, v)
     o = q.r(o.permute(0, 2, 1, 3).reshape(b, n, c))
     if rec is not None:
@@ -219,6 +222,8 @@ def unet1d_forward(p: P, cfg: UNet1dConfig, x: torch.Tensor, t: torch.Tensor,
     every recorded activation whose name is in ``force`` is compared with it (relative L2 error into ``errs``) and
     replaced by it before the next layer runs."""
     q = Storage(storage)
+    if q.bf16 and x.dtype != torch.float32:
+        raise ValueError("the bf16-storage oracle runs on float32 inputs (the float64 run is storage='fp32')")
     g, heads = cfg.resnet_groups, cfg.attention_heads
     n = cfg.num_layers
     pad = cfg.window_length // 2 - cfg.stride // 2

@@ -1,0 +1,90 @@
+"""The constructor and shape sweep of the 1-D U-Net (test infrastructure, see oracle/__init__.py): the configurations that
+tests/test_unet1d_sweep_gpu.py, tests/test_oracle_unet1d_sweep.py and oracle/gen_golden_unet1d_sweep.py share.
+
+T = ``config_tiny``'s structure (multipliers [1, 2, 4, 4], factors [2, 4, 4], blocks [1, 2, 1], attentions [F, T, T], total downsample 64); every
+case names what it changes.  The presets only ever use channels 16 / 64, 8 heads at head dim 32, 8 groups, kernel multiplier 2, factors 2 and 4,
+window 8 / stride 2 / one waveform channel, the scaled skip and the bottleneck transformer.
+
+f83: the 32-channel attention level has head dim 4 with the default 8 heads, which no attention kernel serves (the constructor refuses it), so the
+case runs 4 heads (head dim 8, which no other case or preset has)."""
+from __future__ import annotations
+
+import functools
+from typing import Dict, Tuple
+
+import torch
+
+from audiodiffuser_amd.config import UNet1dConfig
+from audiodiffuser_amd.weights import generate_noise, generate_weights
+
+
+def _t(channels, **kw) -> UNet1dConfig:
+    base = dict(channels=channels, num_filters=channels, multipliers=[1, 2, 4, 4], factors=[2, 4, 4], num_blocks=[1, 2, 1],
+                attentions=[False, True, True])
+    base.update(kw)
+    cfg = UNet1dConfig(**base)
+    cfg.out_channels = cfg.in_channels          # unet1d.py:607
+    return cfg
+
+
+# id -> (configuration, (B, L), weight seed, compute modes)
+CASES: Dict[str, Tuple[UNet1dConfig, Tuple[int, int], int, Tuple[str, ...]]] = {
+    "w24": (_t(24, attention_heads=3), (2, 448), 31, ("fp32", "bf16")),
+    "w48": (_t(48, attention_heads=6), (3, 512), 32, ("fp32", "bf16", "f32x3")),
+    "w32": (_t(32), (3, 512), 33, ("fp32", "bf16")),
+    "h64": (_t(64, attention_heads=4), (3, 1024), 34, ("fp32", "bf16")),
+    "h2": (_t(16, attention_heads=2), (2, 320), 35, ("fp32", "bf16")),
+    "g1": (_t(16, resnet_groups=1), (2, 320), 36, ("fp32", "bf16")),
+    "g16": (_t(32, resnet_groups=16), (2, 320), 37, ("fp32", "bf16")),
+    # odd group counts at lengths whose levels (256 / 128 / 32 / 8) include the short ones (<= 32 rows, a power of two: gn_norm_apply): a group of the skip
+    # concat lies across both sources -- the only group (g1s), or the middle one of three (g3s: widths 48 / 96, groups of 16 / 32 channels, 32 / 64 over a concat)
+    "g1s": (_t(16, resnet_groups=1), (2, 512), 41, ("fp32", "bf16")),
+    "g3s": (_t(24, resnet_groups=3, attention_heads=3), (2, 512), 42, ("fp32", "bf16")),
+    "km4": (_t(16, kernel_multiplier_downsample=4), (2, 576), 38, ("fp32", "bf16")),
+    "f83": (_t(16, multipliers=[1, 2, 4], factors=[8, 3], num_blocks=[3, 1], attentions=[True, False], use_skip_scale=False,
+               use_attention_bottleneck=False, attention_multiplier=4, attention_heads=4), (3, 432), 39, ("fp32", "bf16")),
+    "win16": (_t(16, num_filters=32, multipliers=[2, 2, 4], factors=[2, 2], num_blocks=[1, 1], attentions=[False, True], window_length=16,
+                 stride=4, in_channels=2, attention_multiplier=1), (2, 176), 40, ("fp32", "bf16")),
+}
+
+
+def inputs(cfg: UNet1dConfig, shape, seed: int = 0):
+    """x [B, in_channels, L] and one time per sample (c_noise of the EDM wrapper lies in about [-1.6, 1.1])."""
+    b, l = shape
+    x = generate_noise(5000 + 17 * seed, b, l, channels=cfg.in_channels) * 0.7
+    t = torch.linspace(-1.3, 0.9, b) if b > 1 else torch.tensor([0.35])
+    return x, t
+
+
+def rel(a: torch.Tensor, b: torch.Tensor) -> float:
+    """max |a - b| / max |b| in float64: the metric of the fp32 bars (tests/gpu_helpers.py rel_err)."""
+    return float((a.double() - b.double()).abs().max() / (b.double().abs().max() + 1e-12))
+
+
+@functools.lru_cache(maxsize=None)
+def weights(cid: str):
+    cfg, _, seed, _ = CASES[cid]
+    w = generate_weights(cfg, seed=seed)
+    return w, {k: v.double() for k, v in w.items()}
+
+
+def float64_run(cfg, w, w64, x, t):
+    """-> (float64 output, {name: float64 tensor} for every name the oracle records, {name: fp32-oracle-vs-float64-oracle distance} with "out")."""
+    from oracle import unet1d as O
+    t32, t64 = {}, {}
+    with torch.no_grad():
+        y32 = O.unet1d_forward(w, cfg, x, t, taps=t32)
+        y64 = O.unet1d_forward(w64, cfg, x.double(), t.double(), taps=t64)
+    assert y64.dtype == torch.float64 and all(v.dtype == torch.float64 for v in t64.values()) and list(t32) == list(t64)
+    dist = {k: rel(t32[k], t64[k]) for k in t64}
+    dist["out"] = rel(y32, y64)
+    return y64, t64, dist
+
+
+@functools.lru_cache(maxsize=None)
+def float64_case(cid: str):
+    """``float64_run`` of a sweep case on its own inputs, computed once per session."""
+    cfg, shape, seed, _ = CASES[cid]
+    w, w64 = weights(cid)
+    x, t = inputs(cfg, shape, seed)
+    return float64_run(cfg, w, w64, x, t)

@@ -3,12 +3,14 @@ and compare every recorded activation ("tap") with the CPU oracle on the same in
 from __future__ import annotations
 
 import re
+import time
 
 import torch
 
 import audiodiffuser_amd as A
 from audiodiffuser_amd.weights import generate_weights, generate_noise
 from oracle import unet1d as O
+from oracle import unet1d_sweep as SW
 
 
 def rel_err(a: torch.Tensor, b: torch.Tensor) -> float:
@@ -93,3 +95,84 @@ def conv2d_trace_lines(stderr: str):
             assert m, f"unparsed route line: {l!r}"
             lines.append(dict(zip(_C2_KEYS, map(int, m.groups()[1:])), route=m.group(1)))
     return lines
+
+
+_GEMM_LINE = re.compile(r"^\[adf gemm\] (\S+)\s+B=(\d+) lin=(\d+) mrows=(\d+) n=(\d+)/(\d+) nseg=(\d+) seg0\(c=(\d+)\+(\d+) taps=(\d+) stride=(\d+) off0=(-?\d+) step=(-?\d+) ab=(\d+) act=(\d+)\)"
+                        r"(?: seg1\(c=(\d+)\+(\d+) taps=(\d+) ab=(\d+)\))? res=(\d+) gelu=(\d+) scatter=(\d+) out=(\d+)x(\d+) stats=(\d+) flat=(\d+) tile=(\d+)x(\d+)$")
+_GEMM_KEYS = ("B", "lin", "mrows", "n", "n_pad", "nseg", "c0", "c1", "taps", "stride", "off0", "step", "ab", "act", "s1c0", "s1c1", "s1taps", "s1ab",
+              "res", "gelu", "scatter", "out_rows", "out_c", "stats", "flat", "tm", "tn")
+
+
+def gemm_trace_lines(stderr: str):
+    """The ``[adf gemm]`` lines a process started with ADF_GEMM_TRACE=1 wrote (one per launch_conv_gemm call), as dicts: "route" plus the integers of
+    the line (the second segment's are 0 where there is none).  A line of that prefix that does not parse is an error, so a change of the trace format
+    cannot silently empty a route census."""
+    lines = []
+    for l in stderr.splitlines():
+        if l.startswith("[adf gemm]"):
+            m = _GEMM_LINE.match(l.strip())
+            assert m, f"unparsed route line: {l!r}"
+            lines.append(dict(zip(_GEMM_KEYS, (int(v) if v is not None else 0 for v in m.groups()[1:])), route=m.group(1)))
+    return lines
+
+
+# ---------------------------------------------------------------- the 1-D constructor and shape sweep (tests/test_unet1d_sweep_gpu.py and its child script)
+def sweep_make(cfg, w, dtype, flags=0):
+    net = A.UNet1dBase.from_config(cfg, compute_dtype=dtype, native_flags=flags)
+    net.load_state_dict(w, strict=True)
+    return net.cuda()
+
+
+SWEEP_TROUBLE = []        # a device run that raised (a refusal of the library, or a fault that surfaces as an ordinary error): the caller starts nothing after it
+
+
+def sweep_device_run(net, x, t):
+    """-> (output, {name: recorded tensor}, names in walk order), all on the host."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    try:
+        with torch.no_grad():
+            y = net(x.cuda(), t.cuda())
+        torch.cuda.synchronize()
+    except Exception as e:
+        # a refusal of the library ("<launcher>: <reason>") leaves the device as it was; anything else, or a HIP call that failed, may not
+        if type(e).__name__ != "AdfError" or any(s in str(e).lower() for s in ("hip", "failed", "illegal", "fault")):
+            SWEEP_TROUBLE.append(f"{type(e).__name__}: {e}")
+        raise
+    hd = net.native(dev)
+    names = hd.tap_names()
+    assert len(names) == len(set(names))
+    got = {k: hd.tap(k, x.shape[0], dev).cpu() for k in names}
+    return y.cpu(), got, names
+
+
+def sweep_fp32_report(cfg, w, w64, x, t, net, oracle=None):
+    """fp32 / f32x3 device run against the float64 oracle.  ``oracle``: a (y64, taps64, dist) triple already computed for these inputs."""
+    t0 = time.time()
+    y, got, names = sweep_device_run(net, x, t)
+    t1 = time.time()
+    y64, t64, dist = oracle if oracle is not None else SW.float64_run(cfg, w, w64, x, t)
+    missing = [k for k in names if k not in t64]
+    errs = {}
+    for k in names:
+        if k in t64:
+            assert got[k].shape == t64[k].shape, (k, got[k].shape, t64[k].shape)
+            errs[k] = SW.rel(got[k], t64[k]) if bool(torch.isfinite(got[k]).all()) else float("inf")
+    assert y.shape == y64.shape
+    return {"taps": errs, "names": names, "missing": missing, "out": SW.rel(y, y64) if bool(torch.isfinite(y).all()) else float("inf"),
+            "oracle_dist": max(dist.values()), "ref_absmax": min(float(v.abs().max()) for v in t64.values()),
+            "device_seconds": t1 - t0, "oracle_seconds": time.time() - t1, "y": y, "got": got}
+
+
+def sweep_bf16_report(cfg, w, x, t, net):
+    """bf16 device run, every stored tensor teacher-forced against the bf16-storage oracle."""
+    t0 = time.time()
+    y, got, names = sweep_device_run(net, x, t)
+    t1 = time.time()
+    forced = {}
+    with torch.no_grad():
+        y_f = O.unet1d_forward(w, cfg, x, t, storage="bf16", force=got, errs=forced)
+    missing = sorted(set(got) - set(forced))
+    finite = bool(torch.isfinite(y).all()) and all(bool(torch.isfinite(v).all()) for v in got.values())
+    return {"taps": forced, "names": names, "missing": missing, "out": O.rel_l2(y, y_f) if finite else float("inf"),
+            "ref_absmax": min(float(v.abs().max()) for v in got.values()), "device_seconds": t1 - t0, "oracle_seconds": time.time() - t1,
+            "y": y, "got": got}
