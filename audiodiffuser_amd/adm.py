@@ -36,7 +36,8 @@ def _init_like_reference(name: str, shape, kind: str) -> torch.Tensor:
 
 
 class UNetModel(HipNet):
-    """HIP-backed ``UNetModel``.  Extra kwarg: ``compute_dtype`` in {"fp32", "bf16"} (bf16 needs ``model_channels`` % 64 == 0)."""
+    """HIP-backed ``UNetModel``.  Extra kwarg: ``compute_dtype`` in {"fp32", "bf16", "f32x3"}: bf16 needs ``model_channels`` % 64 == 0; "f32x3" is the
+    split-bf16 mode (fp32 storage and the fp32 width rule, every conv and the head-dim-32 attention on bf16 hi + lo operands, three bf16 MFMAs per product)."""
 
     def __init__(self, image_size=256, in_channels=2, model_channels=128, out_channels=2, num_res_blocks=2, attention_resolutions="16",
                  dropout=0, channel_mult=(1, 2, 2, 4), conv_resample=True, num_classes=None, cond_drop_prob=0.0, use_checkpoint=False,

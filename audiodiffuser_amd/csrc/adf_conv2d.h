@@ -3,7 +3,7 @@
 //
 // Layout: activations are channels-last [B][H*W][C] ("NHWC", fp32 or bf16); the boundary tensors keep the reference's
 // [B][C][H][W] fp32.  A 3x3 / 1x1 convolution is an implicit GEMM over pixels (M) x output channels (N) x (taps x Cin) (K) on
-// MFMA (32x32x16 bf16 / exact-fp32 32x32x2 f32), with the weights in the packed layout of launch_pack_weight
+// MFMA (32x32x16 bf16 / exact-fp32 32x32x2 f32 / split bf16: three 32x32x16 bf16 per product), with the weights in the packed layout of launch_pack_weight
 // ([64- or 32-channel chunk][tap][Cout padded to 32][128-byte row]: a (Cout, Cin, 3, 3) tensor is the (Cout, Cin, 9) conv1d case).
 #pragma once
 #include "adf_common.h"
@@ -31,7 +31,9 @@ struct Conv2dArgs {
     double* stats;          // optional [B][stats_groups][2]: (sum, sumsq) of the STORED output (after bias and residual) per GroupNorm group,
     int stats_groups;       // accumulated with fp64 atomics into a pre-zeroed buffer -- the statistics the next GroupNorm reads
 };
-const char* launch_conv2d(const Conv2dArgs& a, int bf16, hipStream_t s);
+// dtype: 0 = fp32 (exact-fp32 MFMA), 1 = bf16 storage, 2 = fp32 storage with split-bf16 operands (f32x3_t, adf_common.h: the weights packed by
+// launch_pack_weight(.., 2, ..); everything the fp32 mode accepts; ADF_C2_TRACE labels end in ".x3")
+const char* launch_conv2d(const Conv2dArgs& a, int dtype, hipStream_t s);
 
 // First conv (:467-469) straight from the fp32 [B][Cin][H][W] input with the EDM c_in scaling fused (Cin small: vector kernel).  stats (optional,
 // pre-zeroed [B][cout / fg][2]): the FINE GroupNorm statistics of the stored output, reduced in the store when a workgroup's pixels lie in one

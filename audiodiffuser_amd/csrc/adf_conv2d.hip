@@ -142,9 +142,24 @@ __device__ __forceinline__ void c2_store_tile(const Conv2dArgs& a, char* lds, in
     }
 }
 
+// Split-bf16 instantiations (T = f32x3_t, adf_common.h): tensors, gather, prologue and epilogue are the fp32 ones; a staged activation row is split in registers
+// on its way into LDS (hi parts in 16-byte slots 0-3, lo parts in slots 4-7: the thread that holds channels 4 c .. 4 c + 3 of the chunk writes 8 bytes at
+// c * 8 and 8 bytes at 64 + c * 8), the weight rows arrive split (pack_weight_kernel<f32x3_t>), and a K step of 16 channels is three bf16 MFMAs into
+// the same accumulators, small terms first: lo hi, hi lo, hi hi (adf_gemm_rbx3.h).
+template <typename T> struct C2Stored { typedef T type; };
+template <> struct C2Stored<f32x3_t> { typedef float type; };
+__device__ __forceinline__ void c2_split_store(char* row, int c, const float* f, bool zero) {
+    u32x2_t hi = {0u, 0u}, lo = {0u, 0u};
+    if (!zero) split_bf16x4(f, hi, lo);
+    *(u32x2_t*)(row + c * 8) = hi;
+    *(u32x2_t*)(row + 64 + c * 8) = lo;
+}
+
 template <typename T, int TM>
 __global__ void __launch_bounds__(TM * 4) conv2d_gemm_kernel(const Conv2dArgs a) {
     constexpr bool kBf16 = sizeof(T) == 2;
+    constexpr bool kX3 = IsX3<T>::value;
+    typedef typename C2Stored<T>::type S;              // what the tensors hold
     constexpr int EPC = Elem<T>::kPerChunk;
     constexpr int KC = 128 / (int)sizeof(T);           // channels per K chunk
     constexpr int TN = 128;
@@ -227,9 +242,10 @@ __global__ void __launch_bounds__(TM * 4) conv2d_gemm_kernel(const Conv2dArgs a)
 #pragma unroll
         for (int k = 0; k < NA; ++k) {
             u32x4_t v = ra[k];
+            float f[EPC];
+            if (kX3) unpack16<T>(v, f);
             if (!va[k]) v = u32x4_t{0u, 0u, 0u, 0u};                     // zero padding, applied after the activation
             else if (a.ab) {
-                float f[EPC];
                 unpack16<T>(v, f);
                 const float* const ab = abs_ + (ck * KC + c16 * EPC) * 2;
 #pragma unroll
@@ -239,7 +255,8 @@ __global__ void __launch_bounds__(TM * 4) conv2d_gemm_kernel(const Conv2dArgs a)
                 }
                 v = pack16<T>(f);
             }
-            *(u32x4_t*)(st + (srow + RPT * k) * kC2Pitch + c16 * 16) = v;
+            if constexpr (kX3) c2_split_store(st + (srow + RPT * k) * kC2Pitch, c16, f, !va[k]);
+            else *(u32x4_t*)(st + (srow + RPT * k) * kC2Pitch + c16 * 16) = v;
         }
 #pragma unroll
         for (int k = 0; k < NW; ++k) *(u32x4_t*)(st + (TM + srow + RPT * k) * kC2Pitch + c16 * 16) = wok[k] ? rw[k] : u32x4_t{0u, 0u, 0u, 0u};
@@ -272,6 +289,21 @@ __global__ void __launch_bounds__(TM * 4) conv2d_gemm_kernel(const Conv2dArgs a)
                     acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc[j], 0, 0, 0);
                 }
             }
+        } else if constexpr (kX3) {
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                const c2_bf16x8_t fah = *(const c2_bf16x8_t*)(aRow + (ks * 2 + h) * 16), fal = *(const c2_bf16x8_t*)(aRow + (4 + ks * 2 + h) * 16);
+                c2_bf16x8_t fbh[2], fbl[2];
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    fbh[j] = *(const c2_bf16x8_t*)(wRow + j * 32 * kC2Pitch + (ks * 2 + h) * 16);
+                    fbl[j] = *(const c2_bf16x8_t*)(wRow + j * 32 * kC2Pitch + (4 + ks * 2 + h) * 16);
+                }
+#pragma unroll
+                for (int m = 0; m < 3; ++m)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(m == 0 ? fal : fah, m == 1 ? fbl[j] : fbh[j], acc[j], 0, 0, 0);
+            }
         } else {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
@@ -297,8 +329,8 @@ __global__ void __launch_bounds__(TM * 4) conv2d_gemm_kernel(const Conv2dArgs a)
     // ---- epilogue: accumulators (+ bias) -> LDS tile -> 16-byte pieces (+ residual) -> global ---------------------------------
     // (accumulator layout: column r, rows (q & 3) + 8 (q >> 2) + 4 h)
     auto pixg = [&](int row) { return (size_t)(m0 + row); };
-    C2Res<T, TM, TN, NT> pre;
-    c2_res_prefetch<T, TM, TN, NT>(a, tid, n0, (const T*)a.res, pixg, pre);
+    C2Res<S, TM, TN, NT> pre;
+    c2_res_prefetch<S, TM, TN, NT>(a, tid, n0, (const S*)a.res, pixg, pre);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int lc = wn * 64 + j * 32 + r;
@@ -312,7 +344,7 @@ __global__ void __launch_bounds__(TM * 4) conv2d_gemm_kernel(const Conv2dArgs a)
         }
     }
     __syncthreads();
-    c2_store_tile<T, TM, TN, NT>(a, lds, PO, tid, n0, (int)(m0 / HW), (T*)a.out, (const T*)a.res, pixg, pre);
+    c2_store_tile<S, TM, TN, NT>(a, lds, PO, tid, n0, (int)(m0 / HW), (S*)a.out, (const S*)a.res, pixg, pre);
 }
 
 // The same-size 3x3 convs (the two convs of every ResBlock: > 90 % of the network's flops) on SPATIAL tiles: TH x 32 output pixels
@@ -339,6 +371,8 @@ __device__ __forceinline__ void c2_static_for(F&& f) {
 template <typename T, int TH, int WR>
 __global__ void __launch_bounds__(TH / WR * 128) conv2d_tile_kernel(const Conv2dArgs a) {
     constexpr bool kBf16 = sizeof(T) == 2;
+    constexpr bool kX3 = IsX3<T>::value;               // (see conv2d_gemm_kernel)
+    typedef typename C2Stored<T>::type S;
     constexpr int EPC = Elem<T>::kPerChunk;
     constexpr int KC = 128 / (int)sizeof(T);
     constexpr int TW = 32, TM = TH * TW, TN = 128;
@@ -409,9 +443,10 @@ __global__ void __launch_bounds__(TH / WR * 128) conv2d_tile_kernel(const Conv2d
             const int id = tid + k * NT;
             if (id >= HR * 8) continue;
             u32x4_t v = ra[k];
+            float f[EPC];
+            if (kX3) unpack16<T>(v, f);
             if (hoff[k] < 0) v = u32x4_t{0u, 0u, 0u, 0u};                 // zero padding, applied after the activation
             else if (a.ab && !(ADF_C2_KNOCK & 16)) {
-                float f[EPC];
                 unpack16<T>(v, f);
                 const float* const ab = abs_ + (ck * KC + (id & 7) * EPC) * 2;
 #pragma unroll
@@ -420,6 +455,12 @@ __global__ void __launch_bounds__(TH / WR * 128) conv2d_tile_kernel(const Conv2d
                     f[e] = a.act ? (kBf16 ? silu_f(t) : t / (1.0f + expf(-t))) : t;
                 }
                 v = pack16<T>(f);
+            }
+            if constexpr (kX3) {
+                // the piece leaves as (hi.x, hi.y, lo.x, lo.y): store_a writes the two halves to their slots
+                u32x2_t hi = {0u, 0u}, lo = {0u, 0u};
+                if (hoff[k] >= 0) split_bf16x4(f, hi, lo);
+                v = u32x4_t{hi.x, hi.y, lo.x, lo.y};
             }
             ra[k] = v;
         }
@@ -430,6 +471,10 @@ __global__ void __launch_bounds__(TH / WR * 128) conv2d_tile_kernel(const Conv2d
         for (int k = 0; k < NHP; ++k) {
             const int id = tid + k * NT;
             if (id >= HR * 8) continue;
+            if constexpr (kX3) {
+                *(u32x2_t*)(st + (id >> 3) * kC2Pitch + (id & 7) * 8) = u32x2_t{ra[k].x, ra[k].y};
+                *(u32x2_t*)(st + (id >> 3) * kC2Pitch + 64 + (id & 7) * 8) = u32x2_t{ra[k].z, ra[k].w};
+            } else
             *(u32x4_t*)(st + (id >> 3) * kC2Pitch + (id & 7) * 16) = ra[k];
         }
     };
@@ -528,6 +573,29 @@ __global__ void __launch_bounds__(TH / WR * 128) conv2d_tile_kernel(const Conv2d
                 if ((ADF_C2_KNOCK & 4)) { asm volatile("" :: "v"(fa[ks & 1][0]), "v"(fb[ks & 1][0]), "v"(fb[ks & 1][1])); }
                 __builtin_amdgcn_sched_barrier(0);
             }
+        } else if constexpr (kX3) {
+            // 2 K steps x 3 WR x 2 MFMAs: six (twelve) MFMAs behind every batch of fragment reads, against two (four) in the bf16 loop
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                c2_bf16x8_t fah[WR], fal[WR], fbh[2], fbl[2];
+#pragma unroll
+                for (int i = 0; i < WR; ++i) {
+                    fah[i] = *(const c2_bf16x8_t*)(aRow + i * (TW + 2) * kC2Pitch + (ks * 2 + h) * 16);
+                    fal[i] = *(const c2_bf16x8_t*)(aRow + i * (TW + 2) * kC2Pitch + (4 + ks * 2 + h) * 16);
+                }
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    fbh[j] = *(const c2_bf16x8_t*)(wRow + j * 32 * kC2Pitch + (ks * 2 + h) * 16);
+                    fbl[j] = *(const c2_bf16x8_t*)(wRow + j * 32 * kC2Pitch + (4 + ks * 2 + h) * 16);
+                }
+#pragma unroll
+                for (int m = 0; m < 3; ++m)
+#pragma unroll
+                    for (int i = 0; i < WR; ++i)
+#pragma unroll
+                        for (int j = 0; j < 2; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(m == 0 ? fal[i] : fah[i], m == 1 ? fbl[j] : fbh[j], acc[i][j], 0, 0, 0);
+            }
         } else {
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
@@ -566,11 +634,11 @@ __global__ void __launch_bounds__(TH / WR * 128) conv2d_tile_kernel(const Conv2d
     C2_STAMP(6);
 
     // ---- epilogue through LDS (as conv2d_gemm_kernel): tile rows wm * WR + i, pixel = accumulator row -------------------------------
-    T* const og = (T*)a.out + (size_t)b * a.H * a.W * a.cout;
-    const T* const rg = a.res ? (const T*)a.res + (size_t)b * a.H * a.W * a.cout : nullptr;
+    S* const og = (S*)a.out + (size_t)b * a.H * a.W * a.cout;
+    const S* const rg = a.res ? (const S*)a.res + (size_t)b * a.H * a.W * a.cout : nullptr;
     auto pixt = [&](int row) { return (size_t)(ty0 + row / TW) * a.W + tx0 + (row % TW); };
-    C2Res<T, TM, TN, NT> pre;
-    c2_res_prefetch<T, TM, TN, NT>(a, tid, n0, rg, pixt, pre);
+    C2Res<S, TM, TN, NT> pre;
+    c2_res_prefetch<S, TM, TN, NT>(a, tid, n0, rg, pixt, pre);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int lc = wn * 64 + j * 32 + r;
@@ -587,7 +655,7 @@ __global__ void __launch_bounds__(TH / WR * 128) conv2d_tile_kernel(const Conv2d
     }
     __syncthreads();
     C2_STAMP(7);
-    c2_store_tile<T, TM, TN, NT>(a, lds, PO, tid, n0, b, og, rg, pixt, pre);
+    c2_store_tile<S, TM, TN, NT>(a, lds, PO, tid, n0, b, og, rg, pixt, pre);
     C2_STAMP(8);
 }
 
@@ -617,7 +685,13 @@ static void c2_trace(const char* route, const Conv2dArgs& a) {
                     a.cout, a.taps, a.mode, a.ab != nullptr, a.act, a.res != nullptr, a.stats != nullptr);
 }
 
-const char* launch_conv2d(const Conv2dArgs& a, int bf16, hipStream_t s) {
+// route label of a launch: the split-bf16 instantiations carry a suffix
+#define C2_ROUTE(name) (x3 ? name ".x3" : name)
+#define C2_TILE(TH, WR) (bf16 ? launch_conv2d_tile<bf16_t, TH, WR>(a, s) : launch_conv2d_tile<float, TH, WR>(a, s))
+#define C2_TILE3(TH) (x3 ? launch_conv2d_tile<f32x3_t, TH, 1>(a, s) : C2_TILE(TH, 1))
+const char* launch_conv2d(const Conv2dArgs& a, int dtype, hipStream_t s) {
+    if (dtype < 0 || dtype > 2) return "conv2d: dtype must be 0 (fp32), 1 (bf16) or 2 (split bf16)";
+    const bool bf16 = dtype == 1, x3 = dtype == 2;     // x3: everything the fp32 mode accepts, on the default routes (the A/B-only ones are built for fp32 / bf16)
     const int kc = bf16 ? 64 : 32;
     if (a.taps != 9 && a.taps != 1) return "conv2d: taps must be 9 or 1";
     if (a.taps == 1 && a.mode != 0) return "conv2d: a 1x1 conv has no resampling mode";
@@ -639,36 +713,40 @@ const char* launch_conv2d(const Conv2dArgs& a, int bf16, hipStream_t s) {
         // a workgroup re-reads every weight slab from L2: at 128 pixels per workgroup that stream (16 KB per iteration against 64 MFMAs) runs at
         // the L2 -> CU rate and bounds the kernel; 256 pixels per workgroup halve it
         static const int big = (int)adf_tuning("ADF_CONV2D_TH8", 0);     // measured slower than two 128-pixel workgroups per CU: kept for A/B runs only
-        if (big && a.H % 8 == 0 && px / 256 * ny >= 512) return c2_trace("t8x2", a), bf16 ? launch_conv2d_tile<bf16_t, 8, 2>(a, s) : launch_conv2d_tile<float, 8, 2>(a, s);
+        if (big && !x3 && a.H % 8 == 0 && px / 256 * ny >= 512) return c2_trace("t8x2", a), C2_TILE(8, 2);
         static const int th8w1 = (int)adf_tuning("ADF_CONV2D_TH8W1", 0); // 8 x 32 pixels on sixteen waves, one workgroup per CU (A/B runs)
-        if (th8w1 && a.H % 8 == 0 && px / 256 * ny >= 256) return c2_trace("t8", a), bf16 ? launch_conv2d_tile<bf16_t, 8, 1>(a, s) : launch_conv2d_tile<float, 8, 1>(a, s);
+        if (th8w1 && !x3 && a.H % 8 == 0 && px / 256 * ny >= 256) return c2_trace("t8", a), C2_TILE(8, 1);
         static const int wr2 = (int)adf_tuning("ADF_CONV2D_WR2", 0);     // 64 x 64 wave tiles on four waves (A/B runs)
-        if (wr2 && a.H % 4 == 0 && px / 128 * ny >= 128) return c2_trace("t4x2", a), bf16 ? launch_conv2d_tile<bf16_t, 4, 2>(a, s) : launch_conv2d_tile<float, 4, 2>(a, s);
+        if (wr2 && !x3 && a.H % 4 == 0 && px / 128 * ny >= 128) return c2_trace("t4x2", a), C2_TILE(4, 2);
         // (A/B: 160-pixel tiles also where 128-pixel ones divide the image, for convs of at most this many input channels -- few K iterations per tile, so the
         //  tile's start-up and epilogue weigh most)
         static const int prefer5 = (int)adf_tuning("ADF_CONV2D_PREFER5", 0);
-        if (prefer5 && a.cin <= prefer5 && a.H % 5 == 0 && px / 160 * ny >= 128)
-            return c2_trace("t5", a), bf16 ? launch_conv2d_tile<bf16_t, 5, 1>(a, s) : launch_conv2d_tile<float, 5, 1>(a, s);
-        if (a.H % 4 == 0 && px / 128 * ny >= 128) return c2_trace("t4", a), bf16 ? launch_conv2d_tile<bf16_t, 4, 1>(a, s) : launch_conv2d_tile<float, 4, 1>(a, s);
+        if (prefer5 && !x3 && a.cin <= prefer5 && a.H % 5 == 0 && px / 160 * ny >= 128) return c2_trace("t5", a), C2_TILE(5, 1);
+        if (a.H % 4 == 0 && px / 128 * ny >= 128) return c2_trace(C2_ROUTE("t4"), a), C2_TILE3(4);
         // heights such as 10 (the 80-row mel block three levels down): 160-pixel workgroups instead of 64-pixel ones -- 2.5 x fewer passes over the weights
         static const int th5 = (int)adf_tuning("ADF_CONV2D_TH5", 1);
-        if (th5 && a.H % 5 == 0 && px / 160 * ny >= 128) return c2_trace("t5", a), bf16 ? launch_conv2d_tile<bf16_t, 5, 1>(a, s) : launch_conv2d_tile<float, 5, 1>(a, s);
-        if (a.H % 2 == 0) return c2_trace("t2", a), bf16 ? launch_conv2d_tile<bf16_t, 2, 1>(a, s) : launch_conv2d_tile<float, 2, 1>(a, s);
+        if (th5 && a.H % 5 == 0 && px / 160 * ny >= 128) return c2_trace(C2_ROUTE("t5"), a), C2_TILE3(5);
+        if (a.H % 2 == 0) return c2_trace(C2_ROUTE("t2"), a), C2_TILE3(2);
     }
     // 128-pixel tiles (each weight piece staged once per 128 pixels) when the image divides and the grid still fills the chip
     if (((long long)a.H * a.W) % 128 == 0 && px / 128 * ny >= 512) {
         const dim3 grid((unsigned)(px / 128), ny), blk(512);
-        c2_trace("g128", a);
+        c2_trace(C2_ROUTE("g128"), a);
         if (bf16) hipLaunchKernelGGL((conv2d_gemm_kernel<bf16_t, 128>), grid, blk, 0, s, a);
+        else if (x3) hipLaunchKernelGGL((conv2d_gemm_kernel<f32x3_t, 128>), grid, blk, 0, s, a);
         else hipLaunchKernelGGL((conv2d_gemm_kernel<float, 128>), grid, blk, 0, s, a);
     } else {
         const dim3 grid((unsigned)(px / 64), ny), blk(256);
-        c2_trace("g64", a);
+        c2_trace(C2_ROUTE("g64"), a);
         if (bf16) hipLaunchKernelGGL((conv2d_gemm_kernel<bf16_t, 64>), grid, blk, 0, s, a);
+        else if (x3) hipLaunchKernelGGL((conv2d_gemm_kernel<f32x3_t, 64>), grid, blk, 0, s, a);
         else hipLaunchKernelGGL((conv2d_gemm_kernel<float, 64>), grid, blk, 0, s, a);
     }
     return C2_LAUNCH_CHECK("conv2d");
 }
+#undef C2_ROUTE
+#undef C2_TILE
+#undef C2_TILE3
 
 // ------------------------------------------------------------------------------------------------ first / last conv
 constexpr int kC2InSweeps = 16;

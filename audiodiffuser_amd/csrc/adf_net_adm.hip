@@ -240,7 +240,9 @@ int AdmNet::forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
                 T2 qkv = W.conv(xn, t.qkv, nullptr, 0, 0, nullptr, false);
                 W.tap(ln + ".qkv", qkv.t);         // q | k | v blocks (the rows were permuted at load for the legacy order)
                 T2 att; att.H = x.H; att.W = x.W; att.t = W.new_act(t.c, x.t.L);
-                if (W.live()) W.check(launch_attention(qkv.t.p, att.t.p, h->bf16, B, x.t.L, t.c, t.heads, s));
+                // (split-bf16 mode: the MFMA form at head dim 32 and up to 1024 tokens, the exact kernel otherwise)
+                if (W.live()) W.check(h->x3 ? launch_attention_x3(qkv.t.p, att.t.p, B, x.t.L, t.c, t.heads, s)
+                                            : launch_attention(qkv.t.p, att.t.p, h->bf16, B, x.t.L, t.c, t.heads, s));
                 W.tap(ln + ".att", att.t);
                 x = W.conv(att, t.proj, nullptr, 0, 0, xn.t.p, true);    // the residual is the NORMALISED input (:318-322)
                 W.tap(ln, x.t);
@@ -289,9 +291,9 @@ extern "C" int adf_adm_create(const adf_adm_config* cfg, adf_handle** out) {
     if (create_begin("adf_adm_create", cfg, out)) return 1;
     const adf_adm_config& c = *cfg;
     const int kc = c.dtype == ADF_DTYPE_BF16 ? 64 : 32;
-    if (c.dtype != ADF_DTYPE_F32 && c.dtype != ADF_DTYPE_BF16) { g_create_error = "adf_adm_create: bad dtype"; return 1; }
+    if (c.dtype != ADF_DTYPE_F32 && c.dtype != ADF_DTYPE_BF16 && c.dtype != ADF_DTYPE_F32X3) { g_create_error = "adf_adm_create: bad dtype"; return 1; }
     if (c.n_mult < 1 || c.n_mult > ADF_ADM_MAX_LEVELS || c.num_res_blocks < 1 || c.n_attention_ds < 0 || c.n_attention_ds > ADF_ADM_MAX_LEVELS) { g_create_error = "adf_adm_create: bad level / block counts"; return 1; }
-    if (c.model_channels < 32 || c.model_channels % 32 || c.model_channels % kc || c.model_channels > 256) { g_create_error = "adf_adm_create: model_channels must be a multiple of 32 (fp32) / 64 (bf16), at most 256"; return 1; }
+    if (c.model_channels < 32 || c.model_channels % 32 || c.model_channels % kc || c.model_channels > 256) { g_create_error = "adf_adm_create: model_channels must be a multiple of 32 (fp32, f32x3) / 64 (bf16), at most 256"; return 1; }
     if (c.in_channels < 1 || c.out_channels < 1 || c.out_channels > 4) { g_create_error = "adf_adm_create: in_channels >= 1, 1 <= out_channels <= 4"; return 1; }
     if (c.num_classes < 0) { g_create_error = "adf_adm_create: num_classes must be >= 0"; return 1; }
     for (int i = 0; i < c.n_mult; ++i) if (c.channel_mult[i] < 1) { g_create_error = "adf_adm_create: bad channel_mult"; return 1; }

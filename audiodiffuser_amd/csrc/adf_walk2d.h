@@ -89,7 +89,7 @@ struct Walk2d : Walker {
             g.taps = w.taps; g.mode = mode; g.w = w.w; g.nchunk = w.nchunk; g.bias = w.bias; g.res = res; g.out = y.t.p;
             g.bias_b = bias_b; g.bias_bstride = sample_bias ? film_bs : 0;
             g.stats = y.st; g.stats_groups = w.cout / fg;
-            check(tiled ? launch_conv2d(g, h->bf16, s) : launch_u2d_conv_small(g, s));
+            check(tiled ? launch_conv2d(g, h->gemm_dtype(), s) : launch_u2d_conv_small(g, s));
         }
         return y;
     }

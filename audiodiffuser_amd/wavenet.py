@@ -48,6 +48,8 @@ class WaveNetNoise(HipNet):
         super().__init__()
         if compute_dtype not in _DTYPES:
             raise ValueError(f"compute_dtype must be one of {sorted(_DTYPES)}")
+        if _DTYPES[compute_dtype] == _DTYPES["f32x3"]:
+            raise ValueError("compute_dtype='f32x3': the split-bf16 mode exists for UNet1dBase and UNetModel only; WaveNetNoise runs in 'fp32' or 'bf16'")
         if residual_channels % 32 or not 32 <= residual_channels <= 512:
             raise ValueError("residual_channels must be a multiple of 32 in [32, 512]")
         if _DTYPES[compute_dtype] == _DTYPES["bf16"] and residual_channels not in (64, 128, 256):

@@ -59,7 +59,7 @@ int adf_abi_version(void);
 
 #define ADF_DTYPE_F32 0  /* parity mode: fp32 storage, exact-fp32 MFMA */
 #define ADF_DTYPE_BF16 1 /* throughput mode: bf16 storage, fp32 accumulate */
-#define ADF_DTYPE_F32X3 2 /* split-bf16 mode (UNet1dBase only): fp32 storage as ADF_DTYPE_F32; a GEMM operand x is staged as bf16 hi = rn(x) and
+#define ADF_DTYPE_F32X3 2 /* split-bf16 mode (UNet1dBase and the ADM UNetModel): fp32 storage as ADF_DTYPE_F32; a GEMM operand x is staged as bf16 hi = rn(x) and
                              lo = rn(x - hi) (x = hi + lo to 2^-17) and a product is hi*hi + hi*lo + lo*hi on the bf16 MFMA with fp32 accumulation:
                              ~1e-5 relative per layer against the exact-fp32 mode, inside the 1e-3 bar of the reference comparison, at the bf16 MFMA rate / 3 */
 
@@ -127,7 +127,7 @@ typedef struct adf_adm_config {
     int32_t n_attention_ds; int32_t attention_ds[ADF_ADM_MAX_LEVELS];
     int32_t conv_resample, num_heads, num_head_channels, use_scale_shift_norm, resblock_updown, use_new_attention_order;
     int32_t num_classes;                    /* 0 = unconditional; > 0: LabelEmbedder + adf_set_condition (labels, guidance), as for adf_create */
-    int32_t dtype;
+    int32_t dtype;                          /* ADF_DTYPE_F32, _BF16 or _F32X3 */
 } adf_adm_config;
 
 /* Hyper-parameters of the Imagen-style UNet2dBase (unet2d.py:623-667) in the layout the device runs: memory_efficient, cross-embed initial conv,
@@ -154,7 +154,10 @@ int adf_create(const adf_net_config* cfg, adf_handle** out);
 /* A UNetModel (ADM) handle: x / out of adf_net_forward, adf_denoise, adf_sampler_run are [B][C][H][W] fp32 with L = H * W, the
  * shape given by adf_set_image_shape before the call.  On the device: scale-shift or additive conditioning, conv / pooled resampling, resblock up/down, either
  * attention order, unconditional (BASELINE config 4) or class-conditional.  Debug taps: "input_blocks.<i>", "middle_block",
- * "output_blocks.<i>" (the outputs of the reference's blocks). */
+ * "output_blocks.<i>" (the outputs of the reference's blocks).
+ * dtype: ADF_DTYPE_F32 and ADF_DTYPE_F32X3 need model_channels to be a multiple of 32, ADF_DTYPE_BF16 of 64 (at most 256).  In the split-bf16 mode the
+ * 3x3 / 1x1 convs and the attention at head dim 32 take bf16 hi + lo operands; the first and last conv, the GroupNorm kernels, pooling, nearest
+ * upsampling and the embedding projections are the fp32 ones. */
 int adf_adm_create(const adf_adm_config* cfg, adf_handle** out);
 /* A UNet2dBase handle: the same 2-D conventions as a UNetModel handle (adf_set_image_shape first; H and W multiples of 2^n_levels).
  * forward(x, time = c_noise), optionally class-conditional (adf_set_condition).  Debug taps: "init_conv", "init_resnet_block", "downs.<i>",
