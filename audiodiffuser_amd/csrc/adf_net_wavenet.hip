@@ -123,6 +123,7 @@ extern "C" int adf_wavenet_create(const adf_wavenet_config* cfg, adf_handle** ou
     if (create_begin("adf_wavenet_create", cfg, out)) return 1;
     const adf_wavenet_config& c = *cfg;
     if (c.residual_channels < 32 || c.residual_channels % 32 || c.residual_channels > 512) { g_create_error = "adf_wavenet_create: residual_channels must be a multiple of 32 in [32, 512]"; return 1; }
+    // (WaveNetNoise.__init__ in wavenet.py refuses the same two ranges at construction, by name: keep them in step)
     if (c.residual_layers < 1 || c.residual_layers > 1024 || c.dilation_cycle < 1 || c.dilation_cycle > 24) { g_create_error = "adf_wavenet_create: bad residual_layers / dilation_cycle"; return 1; }
     if (c.dim_in < 4 || c.dim_in % 2 || c.dim_in > 1024 || c.dim_mid < 1 || c.dim_mid > 1024 || c.dim_out < 4 || c.dim_out % 4 || c.dim_out > 1024) { g_create_error = "adf_wavenet_create: bad embedding widths"; return 1; }
     if (c.dtype != ADF_DTYPE_F32 && c.dtype != ADF_DTYPE_BF16) { g_create_error = "adf_wavenet_create: bad dtype"; return 1; }

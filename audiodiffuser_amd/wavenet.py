@@ -41,7 +41,7 @@ def _init_like_reference(name: str, shape, kind: str) -> torch.Tensor:
 
 class WaveNetNoise(HipNet):
     """HIP-backed ``WaveNetNoise``.  Extra kwarg: ``compute_dtype`` in {"fp32", "bf16"} (bf16 = MFMA kernels, needs
-    ``residual_channels=256``)."""
+    ``residual_channels`` of 64, 128 or 256).  What ``adf_wavenet_create`` would refuse is refused here, with the argument named."""
 
     def __init__(self, residual_channels: int = 256, residual_layers: int = 36, dilation_cycle: int = 12,
                  compute_dtype: str = "fp32"):
@@ -54,6 +54,11 @@ class WaveNetNoise(HipNet):
             raise ValueError("residual_channels must be a multiple of 32 in [32, 512]")
         if _DTYPES[compute_dtype] == _DTYPES["bf16"] and residual_channels not in (64, 128, 256):
             raise ValueError("the bf16 (MFMA) kernels are built for residual_channels = 64, 128 or 256; use compute_dtype='fp32' otherwise")
+        # the two ranges below are those of adf_wavenet_create (csrc/adf_net_wavenet.hip), which would refuse only at the first forward: keep them in step
+        if not 1 <= residual_layers <= 1024:
+            raise ValueError(f"residual_layers must lie in [1, 1024], got {residual_layers}")
+        if not 1 <= dilation_cycle <= 24:
+            raise ValueError(f"dilation_cycle must lie in [1, 24] (dilations up to 2^23), got {dilation_cycle}")
         self.compute_dtype = compute_dtype
         self.cfg = WaveNetConfig(residual_channels=residual_channels, residual_layers=residual_layers, dilation_cycle=dilation_cycle)
         specs = wavenet_param_specs(self.cfg)

@@ -126,8 +126,8 @@ def sweep_make(cfg, w, dtype, flags=0):
 SWEEP_TROUBLE = []        # a device run that raised (a refusal of the library, or a fault that surfaces as an ordinary error): the caller starts nothing after it
 
 
-def sweep_device_run(net, x, t):
-    """-> (output, {name: recorded tensor}, names in walk order), all on the host."""
+def sweep_device_run(net, x, t, only=None):
+    """-> (output, {name: recorded tensor}, names in walk order), all on the host.  ``only``: the recorded names to copy back (default: all of them)."""
     dev = torch.device("cuda", torch.cuda.current_device())
     try:
         with torch.no_grad():
@@ -141,7 +141,7 @@ def sweep_device_run(net, x, t):
     hd = net.native(dev)
     names = hd.tap_names()
     assert len(names) == len(set(names))
-    got = {k: hd.tap(k, x.shape[0], dev).cpu() for k in names}
+    got = {k: hd.tap(k, x.shape[0], dev).cpu() for k in names if only is None or k in only}
     return y.cpu(), got, names
 
 
@@ -176,3 +176,47 @@ def sweep_bf16_report(cfg, w, x, t, net):
     return {"taps": forced, "names": names, "missing": missing, "out": O.rel_l2(y, y_f) if finite else float("inf"),
             "ref_absmax": min(float(v.abs().max()) for v in got.values()), "device_seconds": t1 - t0, "oracle_seconds": time.time() - t1,
             "y": y, "got": got}
+
+
+# ---------------------------------------------------------------- the WaveNetNoise width and shape sweep (tests/test_wavenet_sweep_gpu.py and its child script)
+def wn_make(cfg, w, dtype):
+    net = A.WaveNetNoise.from_config(cfg, compute_dtype=dtype)
+    net.load_state_dict(w, strict=True)
+    return net.cuda()
+
+
+def wn_fp32_report(cfg, w, w64, audio, step, net, oracle=None):
+    """fp32 device run against the float64 oracle: the output and every recorded tensor.  ``oracle``: a (y64, taps64, dist) triple already computed for
+    these inputs."""
+    from oracle import wavenet_sweep as WS
+    t0 = time.time()
+    y, got, names = sweep_device_run(net, audio, step)
+    t1 = time.time()
+    y64, t64, _ = oracle if oracle is not None else WS.float64_run(cfg, w, w64, audio, step, fp32_runs=False)
+    missing = [k for k in names if k not in t64]
+    errs = {}
+    for k in names:
+        if k in t64:
+            assert got[k].shape == t64[k].shape, (k, got[k].shape, t64[k].shape)
+            errs[k] = WS.rel(got[k], t64[k]) if bool(torch.isfinite(got[k]).all()) else float("inf")
+    assert y.shape == y64.shape, (y.shape, y64.shape)
+    return {"taps": errs, "names": names, "missing": missing, "out": WS.rel(y, y64) if bool(torch.isfinite(y).all()) else float("inf"),
+            "ref_absmax": min([float(t64[k].abs().max()) for k in names if k in t64] + [float(y64.abs().max())]),
+            "device_seconds": t1 - t0, "oracle_seconds": time.time() - t1, "y": y, "got": got}
+
+
+def wn_bf16_report(cfg, w, audio, step, net, free_running=True):
+    """bf16 device run: every recorded tensor teacher-forced against the bf16-storage oracle (relative L2: one fused layer kernel's own deviation), the
+    output from the device's skip sum, and (``free_running``) the output against the fp32 oracle."""
+    from oracle import wavenet as W
+    t0 = time.time()
+    y, got, names = sweep_device_run(net, audio, step)
+    t1 = time.time()
+    forced = {}
+    with torch.no_grad():
+        y_f = W.wavenet_forward(w, cfg, audio, step, storage="bf16", force=got, errs=forced)
+        y_32 = W.wavenet_forward(w, cfg, audio, step) if free_running else None
+    finite = bool(torch.isfinite(y).all()) and all(bool(torch.isfinite(v).all()) for v in got.values())
+    return {"taps": forced, "names": names, "missing": sorted(set(got) - set(forced)), "out": W.rel_l2(y, y_f) if finite else float("inf"),
+            "net": (W.rel_l2(y, y_32) if finite else float("inf")) if free_running else None,
+            "device_seconds": t1 - t0, "oracle_seconds": time.time() - t1, "y": y, "got": got}

@@ -159,7 +159,12 @@ def test_bf16_other_widths_every_layer_vs_bf16_storage_oracle(width):
 def test_bf16_both_layer_kernel_routes_in_a_child_process(wide):
     """The layer kernel has three routes (128-position tiles, default; 64-position tiles, ADF_WN_WIDE=0; 64-position tiles on four waves, two
     workgroups per CU, ADF_WN_WIDE=2); the switch is read once
-    per process, so each runs in its own child: per-layer teacher-forced deviation, the fp32 path, the free-running bf16 net."""
+    per process, so each runs in its own child: per-layer teacher-forced deviation, the fp32 path, the free-running bf16 net.
+
+    "1+prefetch" sets ADF_WN_PREFETCH=1 but never reaches the prefetch block: the kernel prefetches only when workgroup lin + pf_stride exists, pf_stride is
+    the CU count rounded down to a multiple of 8 (256 on an MI355X), and this case launches ceil(1500 / 128) x 2 = 24 workgroups.  It holds the switch's
+    plumbing (a non-zero pf_stride changes no value); the global_load_lds_dword block itself runs in
+    tests/test_wavenet_sweep_gpu.py::test_bf16_prefetch_that_prefetches_moves_no_value, at 288 workgroups."""
     import json, subprocess, sys
     prefetch = wide.endswith("+prefetch")        # the next-tile L2 prefetch of the 128-position kernel (ADF_WN_PREFETCH=1; off by default: no wall-clock gain)
     wide = wide.split("+")[0]
