@@ -274,6 +274,22 @@ static inline int current_device() {
     if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) d = 0;
     return d;
 }
+// A kernel may use more than 64 KB of dynamic LDS only after its limit has been raised, per device.  Raises it to `Bytes` for every kernel of the
+// list, once per device and list (the latch belongs to the instantiation); false: HIP refused, and the next call tries again.
+template <int Bytes, auto... Kernels>
+inline bool raise_lds_limit() {
+    static bool done[kMaxDevices] = {};
+    bool& d = done[current_device()];
+    if (!d) d = ((hipFuncSetAttribute((const void*)Kernels, hipFuncAttributeMaxDynamicSharedMemorySize, Bytes) == hipSuccess) && ...);
+    return d;
+}
+// compute units of the current device (256 where the query fails): the grid of every persistent kernel
+inline int device_cus() {
+    static int cus[kMaxDevices] = {};
+    int& n = cus[current_device()];
+    if (n == 0 && (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, current_device()) != hipSuccess || n < 1)) n = 256;
+    return n;
+}
 
 // Run-time switches.  ROUTE switches (which of two equivalent kernel routes a layer takes) are read from the environment
 // once per process: the parity tests run both sides of each (ADF_GEMM_PP / _RB / _UP / _WS, ADF_RB_FUSED, ADF_TR_FUSED, and

@@ -665,13 +665,7 @@ static const char* launch_conv2d_tile(const Conv2dArgs& a, hipStream_t s) {
     const size_t stages = (size_t)HR * kC2Pitch + 2 * 128 * kC2Pitch + (size_t)2 * a.cin * 4;
     const size_t otile = (size_t)TH * 32 * (128 * sizeof(T) + 16);
     const size_t lds = stages > otile ? stages : otile;
-    static bool attr_done[kMaxDevices] = {};
-    bool& attr = attr_done[current_device()];
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)conv2d_tile_kernel<T, TH, WR>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return "conv2d_tile: hipFuncSetAttribute failed";
-        attr = true;
-    }
+    if (!raise_lds_limit<160 * 1024, conv2d_tile_kernel<T, TH, WR>>()) return "conv2d_tile: hipFuncSetAttribute failed";
     const dim3 grid((unsigned)(a.B * (a.H / TH) * (a.W / 32)), (unsigned)ceil_div(a.cout, 128)), blk(TH / WR * 128);
     hipLaunchKernelGGL((conv2d_tile_kernel<T, TH, WR>), grid, blk, lds, s, a);
     return C2_LAUNCH_CHECK("conv2d_tile");

@@ -11,7 +11,7 @@
 //   * fragment addresses: with the hi slots at 0-3 and the lo slots at 4-7 the bf16 kernel's four K-step addresses base ^ (ks << 5) ARE (hi K0, hi K1, lo K0, lo K1);
 //   * epilogue: fp32 rows (two 16-byte stores per lane and pass), fp32 residual, statistics from the fp32 values.
 // Weight slabs are pack_weight_kernel<f32x3_t>'s (hi | lo rows, 32 K elements each), DMA'd with the same source-side swizzle.
-// Shapes (try_launch_rbx3): fp32 storage, mrows = lin = out_rows a multiple of 256 (128) with a power-of-two tile count per sample, n = n_pad = out_c in {128, 256}
+// Shapes (rb_shape_ok, adf_gemm.hip): fp32 storage, mrows = lin = out_rows a multiple of 256 (128) with a power-of-two tile count per sample, n = n_pad = out_c in {128, 256}
 // (two N tiles), segment 0 = 3 taps (off0 -1) with the GroupNorm table derived in the kernel + SiLU, or raw; channels per source a multiple of 64, at most 512
 // with a table, at most 1024 raw; optional segment 1 = 1 tap raw, or an identity residual (epilogue).
 #pragma once

@@ -823,14 +823,9 @@ const char* launch_attention(const void* qkv, void* out, int bf16, int B, int N,
         const long long blocks = (long long)((B * heads + ppb - 1) / ppb) * qgroups;
         const size_t lds = (size_t)ppb * dh_ * ((size_t)qtiles * 64 + 8);      // vt[dh][keys padded to 32] + 8 bytes of row padding, per pair
         if (lds > 72 * 1024) return "attention_mfma: V^T does not fit LDS";
-        static bool attr_done[kMaxDevices][3] = {};
-        bool& attr = attr_done[current_device()][dh_ == 64 ? 1 : (nw == 8 ? 2 : 0)];
-        const void* fn = dh_ == 32 ? (nw == 8 ? (const void*)attention_mfma32_kernel<32, 8> : (const void*)attention_mfma32_kernel<32>) : (const void*)attention_mfma32_kernel<64>;
-        if (!attr) {
-            if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess)
-                return "attention_mfma: hipFuncSetAttribute failed";
-            attr = true;
-        }
+        if (!(dh_ == 32 ? (nw == 8 ? raise_lds_limit<72 * 1024, attention_mfma32_kernel<32, 8>>() : raise_lds_limit<72 * 1024, attention_mfma32_kernel<32>>())
+                        : raise_lds_limit<72 * 1024, attention_mfma32_kernel<64>>()))
+            return "attention_mfma: hipFuncSetAttribute failed";
         const float sl2e = (float)(1.4426950408889634 / sqrt((double)dh_));
         if (dh_ == 32 && nw == 8)
             hipLaunchKernelGGL((attention_mfma32_kernel<32, 8>), dim3((unsigned)blocks), dim3(512), lds, s, (const bf16_t*)qkv, (bf16_t*)out, B, N, C, heads, sl2e, qrep);
@@ -860,14 +855,8 @@ const char* launch_attention_x3(const void* qkv, void* out, int B, int N, int C,
     const size_t npad = (size_t)qtiles * 32;
     const size_t lds = (size_t)ppb * ((kg ? 0 : 2 * npad * 80) + 2 * 32 * (npad * 2 + 8));
     if (lds > (kg ? 136 : 80) * 1024 || blocks > 0x7fffffffLL) return launch_attention(qkv, out, 0, B, N, C, heads, s);
-    static bool attr_done[kMaxDevices][2] = {};
-    bool& attr = attr_done[current_device()][kg];
-    if (!attr) {
-        const hipError_t e = kg ? hipFuncSetAttribute((const void*)attention_x3_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 136 * 1024)
-                                : hipFuncSetAttribute((const void*)attention_x3_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        if (e != hipSuccess) return "attention_x3: hipFuncSetAttribute failed";
-        attr = true;
-    }
+    if (!(kg ? raise_lds_limit<136 * 1024, attention_x3_kernel<8, true>>() : raise_lds_limit<80 * 1024, attention_x3_kernel<4, false>>()))
+        return "attention_x3: hipFuncSetAttribute failed";
     const float sl2e = (float)(1.4426950408889634 / sqrt(32.0));
     if (kg) hipLaunchKernelGGL((attention_x3_kernel<8, true>), dim3((unsigned)blocks), dim3(512), lds, s, (const float*)qkv, (float*)out, B, N, C, heads, sl2e, qrep);
     else hipLaunchKernelGGL((attention_x3_kernel<4, false>), dim3((unsigned)blocks), dim3(256), lds, s, (const float*)qkv, (float*)out, B, N, C, heads, sl2e, qrep);

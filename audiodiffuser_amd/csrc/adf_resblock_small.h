@@ -325,16 +325,8 @@ inline size_t resblock_small_lds(int ntok, int cin) {
 
 inline const char* launch_resblock_small(const RbFusedArgs& a, int B, int ntok, int cin, hipStream_t s) {
     if ((ntok != 64 && ntok != 16) || (cin != 256 && cin != 512)) return "resblock_small: unsupported shape";
-    static bool attr_done[kMaxDevices] = {};
-    bool& attr = attr_done[current_device()];
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)resblock_small_kernel<64, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)resblock_small_kernel<64, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)resblock_small_kernel<16, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)resblock_small_kernel<16, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return "resblock_small: hipFuncSetAttribute failed";
-        attr = true;
-    }
+    if (!raise_lds_limit<160 * 1024, resblock_small_kernel<64, 256>, resblock_small_kernel<64, 512>, resblock_small_kernel<16, 256>, resblock_small_kernel<16, 512>>())
+        return "resblock_small: hipFuncSetAttribute failed";
     const size_t lds = resblock_small_lds(ntok, cin);
     if (lds > 160 * 1024) return "resblock_small: LDS budget exceeded";
     const int helpers = B < 256 ? ((256 - B) / 8 > 3 * B / 8 ? 3 * B / 8 : (256 - B) / 8) * 8 : 0;

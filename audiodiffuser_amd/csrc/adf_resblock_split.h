@@ -346,14 +346,8 @@ inline size_t resblock_split_lds(int ntok, int cin) {
 
 template <int NTOK, int CIN>
 inline const char* launch_resblock_split_t(const RbSplitArgs& a, int B, hipStream_t s) {
-    static bool attr_done[kMaxDevices] = {};
-    bool& attr = attr_done[current_device()];
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)resblock_split_kernel<NTOK, CIN, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)resblock_split_kernel<NTOK, CIN, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return "resblock_split: hipFuncSetAttribute failed";
-        attr = true;
-    }
+    if (!raise_lds_limit<160 * 1024, resblock_split_kernel<NTOK, CIN, 1>, resblock_split_kernel<NTOK, CIN, 2>>())
+        return "resblock_split: hipFuncSetAttribute failed";
     const size_t lds = resblock_split_lds(NTOK, CIN);
     if (lds > 160 * 1024) return "resblock_split: LDS budget exceeded";
     hipLaunchKernelGGL((resblock_split_kernel<NTOK, CIN, 1>), dim3(B * 4), dim3(512), lds, s, a);

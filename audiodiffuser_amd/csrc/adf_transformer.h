@@ -433,14 +433,8 @@ inline const char* launch_transformer_small(const TrFusedArgs& a, int B, int nto
     const int mr = ntok < 32 ? 32 : ntok;
     const size_t lds = (size_t)mr * (256 * 2 + 16) + (size_t)mr * (768 * 2 + 16) + 8 * 1024 + 1280 * 4;   // + the warm-up scratch + LayerNorm parameters
     if (ntok != 64 && ntok != 16) return "transformer_small: 16 or 64 tokens per sample";
-    static bool attr_done[kMaxDevices] = {};
-    bool& attr = attr_done[current_device()];
-    if (!attr) {                                         // both instances need more than the default 64 KB of dynamic LDS
-        if (hipFuncSetAttribute((const void*)transformer_small_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)transformer_small_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return "transformer_small: hipFuncSetAttribute failed";
-        attr = true;
-    }
+    if (!raise_lds_limit<160 * 1024, transformer_small_kernel<64>, transformer_small_kernel<16>>())   // both instances need more than the default 64 KB of dynamic LDS
+        return "transformer_small: hipFuncSetAttribute failed";
     // 3 helper workgroups per sample, as far as otherwise idle CUs exist (256 CUs, one workgroup each)
     const int helpers = B < 256 ? ((256 - B) / 8 > 3 * B / 8 ? 3 * B / 8 : (256 - B) / 8) * 8 : 0;
     TrFusedArgs aa = a;
@@ -453,14 +447,7 @@ inline const char* launch_transformer_small(const TrFusedArgs& a, int B, int nto
 // 256-token (or longer) samples: MODE 1 / MODE 2 over 64-row tiles (rows = B * tokens, a multiple of 64)
 inline const char* launch_transformer_tiles(const TrFusedArgs& a, int rows, int tokens, int mode, hipStream_t s) {
     if (rows % 64 || tokens % 64 || (mode != 1 && mode != 2)) return "transformer_tiles: unsupported shape";
-    static bool attr_done[kMaxDevices] = {};
-    bool& attr = attr_done[current_device()];
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)transformer_small_kernel<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)transformer_small_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return "transformer_tiles: hipFuncSetAttribute failed";
-        attr = true;
-    }
+    if (!raise_lds_limit<160 * 1024, transformer_small_kernel<64, 1>, transformer_small_kernel<64, 2>>()) return "transformer_tiles: hipFuncSetAttribute failed";
     const size_t lds = (size_t)64 * (256 * 2 + 16) + (size_t)64 * (768 * 2 + 16) + 8 * 1024 + 1280 * 4;
     const int tiles = rows / 64;
     const int helpers = tiles < 256 ? ((256 - tiles) / 8 > 3 * tiles / 8 ? 3 * tiles / 8 : (256 - tiles) / 8) * 8 : 0;

@@ -770,20 +770,11 @@ const char* launch_wn_layer(const WnIO& io, const WnLayerArgs& a, hipStream_t s)
         // launch takes the same 3.56-3.60 ms: the clock the chip holds falls from 2.13 to 1.92 GHz (0.47 -> 0.52 ns per cycle).  The layer kernel runs against the
         // power-management loop, not against its own stalls, exactly as the resblock conv kernel: removed wait cycles come back as frequency.
         static const int wn_pf = adf_route_switch("ADF_WN_PREFETCH", 0);
-        static int num_cu_dev[kMaxDevices] = {};
-        int& ncu = num_cu_dev[current_device()];
-        if (ncu == 0 && (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, current_device()) != hipSuccess || ncu < 8)) ncu = 256;
+        const int ncu = device_cus() < 8 ? 256 : device_cus();      // (fewer than 8 CUs would round the stride down to 0)
         int pf_stride = wn_pf ? ncu / 8 * 8 : 0;
         constexpr int C = 256, TM = 64, TMW = 128;
         if (io.C == 128 || io.C == 64) {                   // other widths: the 128-position kernel with C / 32 waves
-            static bool attr_n[kMaxDevices] = {};
-            bool& an = attr_n[current_device()];
-            if (!an) {
-                if (hipFuncSetAttribute((const void*)wn_layer_bf16_wide_kernel<128, TMW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)wn_layer_bf16_wide_kernel<64, TMW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                    return "wn_layer: hipFuncSetAttribute failed";
-                an = true;
-            }
+            if (!raise_lds_limit<160 * 1024, wn_layer_bf16_wide_kernel<128, TMW>, wn_layer_bf16_wide_kernel<64, TMW>>()) return "wn_layer: hipFuncSetAttribute failed";
             const dim3 grid(ceil_div(io.T, TMW), io.B);
             constexpr size_t lds128 = (size_t)2 * TMW * (128 * 2 + 16) + 6 * 128 * 4 + 2048, lds64 = (size_t)2 * TMW * (64 * 2 + 16) + 6 * 64 * 4 + 2048;
             if (io.C == 128)
@@ -796,26 +787,13 @@ const char* launch_wn_layer(const WnIO& io, const WnLayerArgs& a, hipStream_t s)
         }
         if (io.C != C) return "WaveNet bf16 mode: the MFMA layer kernels are built for residual_channels = 64, 128 or 256 (use fp32 for other widths)";
         const size_t lds = (size_t)4 * TM * WnTile<C, TM>::PA + 6 * C * 4;
-        static bool attr_done[kMaxDevices] = {};
-        bool& attr = attr_done[current_device()];
-        if (!attr) {
-            if (hipFuncSetAttribute((const void*)wn_layer_bf16_kernel<C, TM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                hipFuncSetAttribute((const void*)wn_layer_bf16_wide_kernel<C, TMW>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return "wn_layer: hipFuncSetAttribute failed";
-            attr = true;
-        }
+        if (!raise_lds_limit<160 * 1024, wn_layer_bf16_kernel<C, TM>, wn_layer_bf16_wide_kernel<C, TMW>>()) return "wn_layer: hipFuncSetAttribute failed";
         // route switch (the parity tests run both): 1 = 128-position tiles, 0 = 64-position tiles
         static const int wide = adf_route_switch("ADF_WN_WIDE", 1);
         if (wide == 2) {
             // 64-position tiles on four waves (64 gate + 64 filter columns each): 74 KB of LDS, so a CU holds TWO workgroups and one's staging / gate /
             // epilogue runs under the other's GEMMs -- at twice the weight stream per position
-            static bool attr2[kMaxDevices] = {};
-            bool& a2 = attr2[current_device()];
-            if (!a2) {
-                if (hipFuncSetAttribute((const void*)wn_layer_bf16_wide_kernel<C, TM, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                    return "wn_layer: hipFuncSetAttribute failed";
-                a2 = true;
-            }
+            if (!raise_lds_limit<160 * 1024, wn_layer_bf16_wide_kernel<C, TM, 64>>()) return "wn_layer: hipFuncSetAttribute failed";
             const size_t lds2 = (size_t)2 * TM * WnTile<C, TM>::PA + 6 * C * 4 + 2048;
             hipLaunchKernelGGL((wn_layer_bf16_wide_kernel<C, TM, 64>), dim3(ceil_div(io.T, TM), io.B), dim3(256), lds2, s, (const bf16_t*)a.y,
                                (bf16_t*)a.y_next, a.skip, a.w1, a.b1, a.w2, a.b2, io.e, io.e_bstride, a.n, a.dilation, a.first, io.T, 2 * pf_stride);
@@ -833,13 +811,7 @@ const char* launch_wn_layer(const WnIO& io, const WnLayerArgs& a, hipStream_t s)
     }
     if (io.C % 32 || io.C > 512) return "WaveNet fp32 mode: residual_channels must be a multiple of 32, at most 512";
     const size_t lds = (size_t)4 * io.C * kWnTP * 4;
-    static bool attr_done32[kMaxDevices] = {};
-    bool& attr = attr_done32[current_device()];
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)wn_layer_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return "wn_layer: hipFuncSetAttribute failed";
-        attr = true;
-    }
+    if (!raise_lds_limit<160 * 1024, wn_layer_f32_kernel>()) return "wn_layer: hipFuncSetAttribute failed";
     hipLaunchKernelGGL(wn_layer_f32_kernel, dim3(ceil_div(io.T, kWnTP), io.B), dim3(io.C), lds, s, (const float*)a.y, (float*)a.y_next, a.skip,
                        (const float*)a.w1, a.b1, (const float*)a.w2, a.b2, io.e, io.e_bstride, a.n, a.dilation, a.first, io.T, io.C);
     return WN_LAUNCH_CHECK("wn_layer_f32");
@@ -958,14 +930,7 @@ const char* launch_wn_final(const WnIO& io, const WnFinalArgs& a, hipStream_t s)
     if (io.bf16) {
         constexpr int C = 256, TM = 64;
         if (io.C == 128 || io.C == 64) {
-            static bool attr_n[kMaxDevices] = {};
-            bool& an = attr_n[current_device()];
-            if (!an) {
-                if (hipFuncSetAttribute((const void*)wn_final_bf16_kernel<128, TM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-                    hipFuncSetAttribute((const void*)wn_final_bf16_kernel<64, TM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                    return "wn_final: hipFuncSetAttribute failed";
-                an = true;
-            }
+            if (!raise_lds_limit<160 * 1024, wn_final_bf16_kernel<128, TM>, wn_final_bf16_kernel<64, TM>>()) return "wn_final: hipFuncSetAttribute failed";
             const dim3 grid(ceil_div(io.T, TM), io.B);
             constexpr size_t lds128 = (size_t)TM * (128 * 2 + 16) + (2 * 128 + 4 * TM) * 4, lds64 = (size_t)TM * (64 * 2 + 16) + (2 * 64 + 2 * TM) * 4;
             if (io.C == 128)
@@ -978,13 +943,7 @@ const char* launch_wn_final(const WnIO& io, const WnFinalArgs& a, hipStream_t s)
         }
         if (io.C != C) return "WaveNet bf16 mode: built for residual_channels = 64, 128 or 256";
         const size_t lds = (size_t)TM * WnTile<C, TM>::PA + (2 * C + 8 * TM) * 4;
-        static bool attr_done[kMaxDevices] = {};
-        bool& attr = attr_done[current_device()];
-        if (!attr) {
-            if (hipFuncSetAttribute((const void*)wn_final_bf16_kernel<C, TM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-                return "wn_final: hipFuncSetAttribute failed";
-            attr = true;
-        }
+        if (!raise_lds_limit<160 * 1024, wn_final_bf16_kernel<C, TM>>()) return "wn_final: hipFuncSetAttribute failed";
         hipLaunchKernelGGL((wn_final_bf16_kernel<C, TM>), dim3(ceil_div(io.T, TM), io.B), dim3(512), lds, s, a.skip, a.skip_scale, a.w_sp, a.b_sp,
                            a.w_out, a.b_out, a.out, a.mode, a.x_noisy, a.coef, a.coef_bstride, io.T);
         return WN_LAUNCH_CHECK("wn_final_bf16");

@@ -2,6 +2,8 @@
 and compare every recorded activation ("tap") with the CPU oracle on the same inputs."""
 from __future__ import annotations
 
+import json
+import os
 import re
 import time
 
@@ -114,6 +116,17 @@ def gemm_trace_lines(stderr: str):
             assert m, f"unparsed route line: {l!r}"
             lines.append(dict(zip(_GEMM_KEYS, (int(v) if v is not None else 0 for v in m.groups()[1:])), route=m.group(1)))
     return lines
+
+
+def assert_gemm_route_trace(case: str, stderr: str):
+    """The ``[adf gemm]`` lines of a child process, verbatim and in order, equal those recorded for the same command in tests/golden/gemm_route_traces.json
+    (its ``_recorded`` entry names the commit and the command lines): the whole route sequence -- kernel, tile, flat, fused statistics of every launch --
+    not a census of subsets.  Routes do not depend on the CU count (only grid sizes do, and the lines do not print them)."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_route_traces.json")) as f:
+        want = json.load(f)[case]
+    got = [l for l in stderr.splitlines() if l.startswith("[adf gemm]")]
+    i = next((k for k, (g, w) in enumerate(zip(got, want)) if g != w), min(len(got), len(want)))
+    assert got == want, f"{case}: {len(got)} route lines against {len(want)} recorded; first difference at line {i}: {got[i:i + 1]} against {want[i:i + 1]}"
 
 
 # ---------------------------------------------------------------- the 1-D constructor and shape sweep (tests/test_unet1d_sweep_gpu.py and its child script)

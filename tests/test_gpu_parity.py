@@ -37,7 +37,7 @@ import torch
 import audiodiffuser_amd as A
 from audiodiffuser_amd import _lib
 from audiodiffuser_amd.weights import generate_noise, generate_weights
-from gpu_helpers import make_net, rel_err, rel_l2, tap_errors, tap_errors_bf16, golden_inputs
+from gpu_helpers import assert_gemm_route_trace, make_net, rel_err, rel_l2, tap_errors, tap_errors_bf16, golden_inputs
 
 pytestmark = pytest.mark.gpu
 FP32_TOL = 1e-3       # the north-star bar; measured ~2e-6
@@ -103,6 +103,7 @@ def test_split_bf16_resblock_dma_kernel_on_small_batches_every_tensor_vs_fp32_or
     r = subprocess.run([sys.executable, os.path.join(root, "tests", "diag", "gpu_forced_report.py"), preset, "8" if preset == "c2" else "4", "16384", "0", "f32x3"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
+    assert_gemm_route_trace("forced_c2_b8_f32x3_rbx3" if preset == "c2" else "forced_c3_b4_f32x3_rbx3", r.stderr)
     rep = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     errs = rep["forced"]
     assert rep["finite"]
@@ -184,10 +185,11 @@ def test_resblock_dma_kernel_on_small_batches_incl_128_row_tiles_every_stored_te
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, ADF_GEMM_RB="2")
+    env = dict(os.environ, ADF_GEMM_RB="2", ADF_GEMM_TRACE="1")
     r = subprocess.run([sys.executable, os.path.join(root, "tests", "diag", "gpu_forced_report.py"), "c2", "8", "16384"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
+    assert_gemm_route_trace("forced_c2_b8_rb", r.stderr)
     rep = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     forced = rep["forced"]
     assert rep["finite"]
@@ -209,6 +211,7 @@ def test_transposed_conv_3tap_form_with_a_group_size_its_epilogue_does_not_reduc
     r = subprocess.run([sys.executable, os.path.join(root, "tests", "diag", "gpu_forced_report.py"), "c2", "4", "16384", "32"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
+    assert_gemm_route_trace("forced_c2_b4_g32_rb", r.stderr)
     rep = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     forced = rep["forced"]
     assert rep["finite"]
@@ -682,10 +685,11 @@ def test_transposed_conv_kernel_matches_the_generic_routes(tmp_path):
     outs = {}
     for mode in ("0", "2"):
         path = str(tmp_path / f"up{mode}.pt")
-        env = dict(os.environ, ADF_GEMM_UP=mode, B="5")
+        env = dict(os.environ, ADF_GEMM_UP=mode, B="5", ADF_GEMM_TRACE="1")
         r = subprocess.run([sys.executable, os.path.join(root, "tests", "diag", "gpu_pp_check.py"), "save", path], env=env, capture_output=True,
                            text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
+        assert_gemm_route_trace("pp_check_b5_up" + mode, r.stderr)
         outs[mode] = torch.load(path)
     a, b = outs["2"], outs["0"]
     assert all(bool(torch.isfinite(v).all()) for v in a.values())

@@ -58,7 +58,7 @@ Route cases (child processes, tests/diag/gpu_unet1d_routes_report.py with ADF_GE
   pp128g1 (bf16, ADF_GEMM_PP=2): channels 64, multipliers [1, 2], factors [2], resnet_groups 1, 32 x 2048: 128 channels at 512 rows, 32 * 4 = 128 tiles of 128 rows.  The
         concat conv1 (128 + 128 channels, its one group across both sources) is declined by conv_gemm_rb_kernel's host check and takes pp with the table from gn_finalize.
         census: pp (128, 3, 1) (128, 3, 2), plain (128, 2, 1).  Worst mid.pre 7.0e-5 (output 1.1e-7).
-  Not reachable off the presets, by the gates: rb / rbx3 (try_launch_rb: n of 128 or 256 only, an even number of 64-channel blocks), up (cin 256 / 128 and cout 256 / 128 / 64
+  Not reachable off the presets, by the gates: rb / rbx3 (rb_shape_ok: n of 128 or 256 only, an even number of 64-channel blocks), up (cin 256 / 128 and cout 256 / 128 / 64
   only), pp in fp32 (bf16 only), ws for a 3-tap conv wider than 6 weight slabs of 128 columns (so no off-preset resblock conv: 192 channels need 9).
 
 That the sweep has teeth was checked once on four value-only edits (not committed), each against every case of test_every_tensor_vs_oracle and the separate-statistics test:
@@ -68,7 +68,7 @@ That the sweep has teeth was checked once on four value-only edits (not committe
   odd-factor transposed conv without its output_padding row caught by f83 fp32 (up0.conv 0.43, 18 of 43 over) and f83 bf16 (up0.conv 0.15 of 5e-4)
   gn_straddle_sums without the skip scale on the second source's sum   caught by g1, g1s, g3s in fp32 (up0.block0.h1 0.032 / 0.012 / 0.010, 31 of 71 over) and bf16
                                                             (up0.block1.h1 0.042, 0.025; g3s up2.block0.h1 0.011 of 5e-4); pp128g1 was not run against an edit: without the
-                                                            decline in settle_gn the pp kernel would read a statistics group past the sample's own, so that edit stayed off the device
+                                                            decline in decide_conv_gemm the pp kernel would read a statistics group past the sample's own, so that edit stayed off the device
 Not attempted: a factor of 1 (the reference's plain Conv1d(k = 3) is not built; the constructor refuses it).
 """
 import functools
@@ -83,7 +83,7 @@ import torch
 
 from audiodiffuser_amd import _lib
 import gpu_helpers as R
-from gpu_helpers import gemm_trace_lines
+from gpu_helpers import assert_gemm_route_trace, gemm_trace_lines
 from oracle import unet1d_sweep as SW
 from test_gpu_parity import FP32_TIGHT, F32X3_TOL, _bf16_tol
 
@@ -213,7 +213,7 @@ def child(case):
     lines = gemm_trace_lines(r.stderr)
     assert rep["case"] == case and lines
     print(case, "child wall s", round(time.time() - t0, 1))
-    return rep, lines
+    return rep, lines, r.stderr
 
 
 def route_of(l):
@@ -239,7 +239,8 @@ def off_preset(lines, route):
 def test_route_ws_plain_and_both_split_k_tiles_at_width_192(dtype):
     """ws192 of the module docstring: the weight-stationary kernel at its tile threshold with a partial second N tile, the plain kernel on 64-column tiles and both
     split-K tile sizes, all at 192 channels; values at the module's bars."""
-    rep, lines = child("ws192_" + dtype)
+    rep, lines, stderr = child("ws192_" + dtype)
+    assert_gemm_route_trace("ws192_" + dtype, stderr)
     req = {("ws", dtype, 192, 3, 1), ("plain", dtype, 192, 3, 1), ("plain", dtype, 192, 3, 2), ("ksplit64", dtype, 192, 3, 2), ("ksplit32", dtype, 192, 3, 2)}
     need(census(lines, dtype), req)
     for route in ("ws", "plain", "ksplit64", "ksplit32"):
@@ -251,7 +252,8 @@ def test_route_ws_plain_and_both_split_k_tiles_at_width_192(dtype):
 
 def test_route_pp_at_width_384():
     """pp384 of the module docstring: the persistent LDS-DMA kernel at 384 channels on 128-row tiles, 132 tiles against the threshold of 128 (ADF_GEMM_PP=2)."""
-    rep, lines = child("pp384_bf16")
+    rep, lines, stderr = child("pp384_bf16")
+    assert_gemm_route_trace("pp384_bf16", stderr)
     need(census(lines, "bf16"), {("pp", "bf16", 384, 3, 1), ("pp", "bf16", 384, 3, 2)})
     pp = off_preset(lines, "pp")
     assert pp and all(l["tm"] == 128 and l["B"] * (l["mrows"] // 128) * (l["n_pad"] // 128) == 132 for l in pp), pp
@@ -260,8 +262,9 @@ def test_route_pp_at_width_384():
 
 def test_route_pp_with_one_group_per_sample_takes_its_table_from_gn_finalize():
     """pp128g1 of the module docstring: a concat conv1 whose single GroupNorm group lies across both sources on the persistent LDS-DMA kernel, which cannot derive
-    that table itself (launch_conv_gemm's settle_gn sends it to gn_finalize); values at the module's bars."""
-    rep, lines = child("pp128g1_bf16")
+    that table itself (decide_conv_gemm's plan sends it to gn_finalize); values at the module's bars."""
+    rep, lines, stderr = child("pp128g1_bf16")
+    assert_gemm_route_trace("pp128g1_bf16", stderr)
     need(census(lines, "bf16"), {("pp", "bf16", 128, 3, 1), ("pp", "bf16", 128, 3, 2)})
     cat = [l for l in lines if l["route"] == "pp" and l["c1"] == 128 and l["ab"] == 1]
     assert cat and all(l["tm"] == 128 and l["B"] * (l["mrows"] // 128) == 128 for l in cat), cat
