@@ -99,6 +99,12 @@ class AdfRunCounters(C.Structure):
                 ("graph_replays", C.c_int64), ("denoise_calls", C.c_int64), ("net_passes", C.c_int64)]
 
 
+class AdfIstftConfig(C.Structure):
+    """``adf_istft_config`` of include/audiodiffuser_amd.h."""
+    _fields_ = [("n_fft", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32), ("normalized", C.c_int32),
+                ("spec_abs_exponent", C.c_double), ("spec_factor", C.c_double)]
+
+
 FLAG_NEAREST_UPSAMPLE = 2  # ADF_FLAG_NEAREST_UPSAMPLE
 PRECOND_EDM, PRECOND_VE, PRECOND_VP, PRECOND_V_EDM = 0, 1, 2, 3      # ADF_PRECOND_* (adf_set_preconditioning)
 ABI_VERSION = 7          # ADF_ABI_VERSION of the header this binding was written against
@@ -141,6 +147,10 @@ EXPORTS = {
                                   C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p]),
     "adf_bench_wavenet_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double), C.c_void_p]),
+    "adf_istft_create": (C.c_int, [C.POINTER(AdfIstftConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "adf_istft_basis": (C.c_int, [C.POINTER(AdfIstftConfig), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "adf_istft_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "adf_istft_destroy": (None, [C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

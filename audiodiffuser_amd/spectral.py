@@ -1,0 +1,125 @@
+"""``SpecToWave``: the sampled complex spectrogram to audio on the device, in one HIP launch (csrc/adf_istft.hip).
+
+Replaces the tail of the reference's ``DiffUnetComplexModule.synthesize_from_noise`` (src/models/diffunet_complex_module.py:90-99)::
+
+    spec  = torch.view_as_complex(spec.permute(0, 2, 3, 1).contiguous())
+    spec  = spec_back(spec, spec_abs_exponent, spec_factor)                       # src/models/utils.py:22-28
+    audio = torch.istft(spec, window=hann(n_fft), normalized=True, n_fft=n_fft, hop_length=hop_length, center=True)
+
+It takes the sampler's ``[B, 2, F, T]`` tensor as it is -- the permute and the complex view are never materialised.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib
+
+
+def _config(n_fft, hop_length, spec_abs_exponent, spec_factor, center, normalized) -> _lib.AdfIstftConfig:
+    return _lib.AdfIstftConfig(n_fft=int(n_fft), hop_length=int(hop_length), center=int(bool(center)), normalized=int(bool(normalized)),
+                               spec_abs_exponent=float(spec_abs_exponent), spec_factor=float(spec_factor))
+
+
+def _host_window(window, n_fft: int) -> Optional[np.ndarray]:
+    if window is None:
+        return None
+    w = np.ascontiguousarray(torch.as_tensor(window).detach().cpu().to(torch.float32).numpy())
+    if w.ndim != 1 or w.shape[0] != int(n_fft):
+        raise ValueError(f"window must hold n_fft = {int(n_fft)} values, got shape {tuple(w.shape)}")
+    return w
+
+
+def _checked(lib, rc: int) -> None:
+    """A refused argument is the caller's mistake: ValueError with the library's message (which names the argument)."""
+    if rc != 0:
+        msg = lib.adf_last_error(None)
+        raise ValueError(msg.decode() if msg else "adf_istft: unknown error")
+
+
+def istft_basis(n_fft: int = 510, hop_length: int = 128, center: bool = True, normalized: bool = True, window=None,
+                spec_abs_exponent: float = 0.2, spec_factor: float = 0.6) -> Tuple[np.ndarray, np.ndarray]:
+    """The host tables a plan is built from (``adf_istft_basis``; no device is touched): ``basis`` fp32 ``[2, D * hop_length, F]`` (cosine rows,
+    then sine rows) and ``wsq`` fp32 ``[D * hop_length]``."""
+    lib = _lib.load_library()
+    cfg = _config(n_fft, hop_length, spec_abs_exponent, spec_factor, center, normalized)
+    w = _host_window(window, n_fft)
+    wp = w.ctypes.data_as(C.c_void_p) if w is not None else None
+    _checked(lib, lib.adf_istft_basis(C.byref(cfg), wp, None, None))
+    rows = -(-cfg.n_fft // cfg.hop_length) * cfg.hop_length
+    basis = np.empty((2, rows, cfg.n_fft // 2 + 1), dtype=np.float32)
+    wsq = np.empty((rows,), dtype=np.float32)
+    _checked(lib, lib.adf_istft_basis(C.byref(cfg), wp, basis.ctypes.data_as(C.c_void_p), wsq.ctypes.data_as(C.c_void_p)))
+    return basis, wsq
+
+
+class SpecToWave(nn.Module):
+    """``forward(pcomplex_spec [B, 2, n_fft / 2 + 1, T] fp32) -> [B, hop_length * (T - 1)] fp32`` on the same ROCm device.
+
+    A module without parameters (hydra ``_target_: audiodiffuser_amd.SpecToWave``).  ``window``: a 1-D tensor of ``n_fft`` values, or None for
+    ``torch.hann_window(n_fft)``.  The result stays on the device, as in ``synthesize_from_noise``; the caller does ``.cpu()``."""
+
+    def __init__(self, n_fft: int = 510, hop_length: int = 128, spec_abs_exponent: float = 0.2, spec_factor: float = 0.6,
+                 center: bool = True, normalized: bool = True, window=None):
+        super().__init__()
+        self.n_fft, self.hop_length = int(n_fft), int(hop_length)
+        self.spec_abs_exponent, self.spec_factor = float(spec_abs_exponent), float(spec_factor)
+        self.center, self.normalized = bool(center), bool(normalized)
+        self._window = _host_window(window, n_fft)
+        self._lib = _lib.load_library()
+        self._cfg = _config(n_fft, hop_length, spec_abs_exponent, spec_factor, center, normalized)
+        _checked(self._lib, self._lib.adf_istft_basis(C.byref(self._cfg), self._window_ptr(), None, None))    # argument checks only
+        self._plans = {}                   # device index -> adf_istft_plan*
+
+    def _window_ptr(self):
+        return self._window.ctypes.data_as(C.c_void_p) if self._window is not None else None
+
+    def _plan(self, device: torch.device) -> C.c_void_p:
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        plan = self._plans.get(idx)
+        if plan is None:
+            plan = C.c_void_p()
+            with torch.cuda.device(idx):   # a plan belongs to the device current at its creation
+                rc = self._lib.adf_istft_create(C.byref(self._cfg), self._window_ptr(), C.byref(plan))
+            if rc != 0:
+                msg = self._lib.adf_last_error(None)
+                raise _lib.AdfError(f"adf_istft_create: {msg.decode() if msg else 'unknown error'}")
+            self._plans[idx] = plan
+        return plan
+
+    def forward(self, pcomplex_spec: torch.Tensor) -> torch.Tensor:
+        x = pcomplex_spec
+        F = self.n_fft // 2 + 1
+        if not torch.is_tensor(x) or x.dim() != 4 or x.shape[1] != 2 or x.shape[2] != F:
+            raise ValueError(f"SpecToWave takes [B, 2, n_fft / 2 + 1 = {F}, T], got {tuple(x.shape) if torch.is_tensor(x) else type(x)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"SpecToWave takes an fp32 tensor, got {x.dtype}")
+        if not x.is_contiguous():
+            raise ValueError("SpecToWave takes a contiguous [B, 2, F, T] tensor (the sampler's output as it is)")
+        B, T = int(x.shape[0]), int(x.shape[3])
+        if B < 1 or T < 2:
+            raise ValueError(f"SpecToWave needs B >= 1 and T >= 2 frames, got B = {B}, T = {T}")
+        if not x.is_cuda:
+            raise RuntimeError("the HIP SpecToWave only runs on a ROCm device ('cuda'); there is no CPU fallback")
+        out = torch.empty((B, self.hop_length * (T - 1)), device=x.device, dtype=torch.float32)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        rc = self._lib.adf_istft_run(self._plan(x.device), x.data_ptr(), B, T, out.data_ptr(), out.shape[1], stream)
+        if rc != 0:
+            msg = self._lib.adf_last_error(None)
+            raise _lib.AdfError(f"adf_istft_run: {msg.decode() if msg else 'unknown error'}")
+        return out
+
+    def extra_repr(self) -> str:
+        return (f"n_fft={self.n_fft}, hop_length={self.hop_length}, spec_abs_exponent={self.spec_abs_exponent}, spec_factor={self.spec_factor}, "
+                f"normalized={self.normalized}")
+
+    def __del__(self):
+        for plan in getattr(self, "_plans", {}).values():
+            try:
+                self._lib.adf_istft_destroy(plan)
+            except Exception:
+                pass

@@ -51,7 +51,8 @@ extern "C" {
  * 6: adf_unet2d_config / adf_unet2d_create (the Imagen-style UNet2dBase, exact fp32).
  * 7: adf_set_preconditioning (ADF_PRECOND_EDM / VE / VP / V_EDM) and adf_debug_coef_rows.  The preconditioning kind travels as handle state, in the
  *    style of adf_set_dynamic_threshold: adf_sampler_desc and the argument list of adf_denoise are unchanged, so a caller that fills only the
- *    fields of version 6 and never calls the setter still gets EluDiffusion's rows. */
+ *    fields of version 6 and never calls the setter still gets EluDiffusion's rows.
+ *    Added without a bump (new symbols only, nothing of the above changes): adf_istft_config and the four adf_istft_* entry points. */
 #define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
@@ -270,6 +271,32 @@ int adf_bench_layer(adf_handle* h, int B, int L, int level, int conv, int iters,
  * on `stream`.  The working set of one launch at bench sizes (y, y_next, fp32 skip sum: > 5 GB at B = 128, T = 22050) is far beyond
  * the 256 MiB Infinity Cache, so no operand rotation is needed. */
 int adf_bench_wavenet_layer(adf_handle* h, int B, int T, int layer, int iters, float* ms, double* algo_bytes, double* flops, void* stream);
+
+/* SpecToWave: the tail of DiffUnetComplexModule.synthesize_from_noise (src/models/diffunet_complex_module.py:90-99) in one launch --
+ * view_as_complex(permute(spec)) + spec_back (src/models/utils.py:22-28) + torch.istft(window, normalized, center=True, length=None).
+ * spec is the sampler's output as it leaves adf_sampler_run: fp32 [B][2][n_fft / 2 + 1][T], channel 0 real, 1 imaginary.  audio is fp32
+ * [B][audio_len] with audio_len = hop_length * (T - 1), 16-byte aligned.  The inverse DFT, the window and the overlap-add are one exact-fp32
+ * MFMA GEMM against a windowed cosine / sine basis built in double on the host.
+ *   n_fft even in [32, 1024]; hop_length a multiple of 32 in [32, 256]; ceil(n_fft / hop_length) <= 8; center must be 1; T >= 2;
+ *   spec_abs_exponent > 0, spec_factor > 0.  window: n_fft floats on the HOST, or NULL for the periodic Hann window; the sum of its shifted
+ *   squares must stay above 1e-11 over the kept samples (torch.istft's NOLA check).
+ * A plan belongs to the device current at adf_istft_create; adf_istft_run makes it current, enqueues on `stream`, and neither allocates nor
+ * synchronises.  Every function returns 0 on success; adf_last_error(NULL) gives the message of the last failure. */
+typedef struct adf_istft_config {
+    int32_t n_fft, hop_length, center, normalized;
+    double spec_abs_exponent, spec_factor;
+} adf_istft_config;
+typedef struct adf_istft_plan adf_istft_plan;
+int adf_istft_create(const adf_istft_config* cfg, const float* window, adf_istft_plan** out);
+/* Host only (touches no device): the tables the plan is built from, with D = ceil(n_fft / hop_length), F = n_fft / 2 + 1, s = sqrt(n_fft) / n_fft when
+ * normalized, else 1 / n_fft, a_0 = a_{F-1} = 1 and every other a_k = 2:
+ *   basis [2][D * hop_length][F]:  basis[0][m][k] = w[m] a_k cos(2 pi m k / n_fft) s,  basis[1][m][k] = -w[m] a_k sin(2 pi m k / n_fft) s, with
+ *                                  basis[1][m][0] = basis[1][m][F-1] = 0 and rows m >= n_fft zero; computed in double, rounded once
+ *   wsq   [D * hop_length]:        w[m]^2, zero for m >= n_fft
+ * Either output may be NULL (both NULL: the arguments are checked and nothing is written). */
+int adf_istft_basis(const adf_istft_config* cfg, const float* window, float* basis, float* wsq);
+int adf_istft_run(adf_istft_plan* plan, const float* spec, int B, int T, float* audio, int64_t audio_len, void* stream);
+void adf_istft_destroy(adf_istft_plan* plan);
 
 #ifdef __cplusplus
 }
