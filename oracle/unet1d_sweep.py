@@ -29,23 +29,44 @@ def _t(channels, **kw) -> UNet1dConfig:
 
 # id -> (configuration, (B, L), weight seed, compute modes)
 CASES: Dict[str, Tuple[UNet1dConfig, Tuple[int, int], int, Tuple[str, ...]]] = {
-    "w24": (_t(24, attention_heads=3), (2, 448), 31, ("fp32", "bf16")),
+    "w24": (_t(24, attention_heads=3), (2, 448), 31, ("fp32", "bf16", "f32x3")),
     "w48": (_t(48, attention_heads=6), (3, 512), 32, ("fp32", "bf16", "f32x3")),
-    "w32": (_t(32), (3, 512), 33, ("fp32", "bf16")),
-    "h64": (_t(64, attention_heads=4), (3, 1024), 34, ("fp32", "bf16")),
-    "h2": (_t(16, attention_heads=2), (2, 320), 35, ("fp32", "bf16")),
-    "g1": (_t(16, resnet_groups=1), (2, 320), 36, ("fp32", "bf16")),
-    "g16": (_t(32, resnet_groups=16), (2, 320), 37, ("fp32", "bf16")),
+    "w32": (_t(32), (3, 512), 33, ("fp32", "bf16", "f32x3")),
+    "h64": (_t(64, attention_heads=4), (3, 1024), 34, ("fp32", "bf16", "f32x3")),
+    "h2": (_t(16, attention_heads=2), (2, 320), 35, ("fp32", "bf16", "f32x3")),
+    "g1": (_t(16, resnet_groups=1), (2, 320), 36, ("fp32", "bf16", "f32x3")),
+    "g16": (_t(32, resnet_groups=16), (2, 320), 37, ("fp32", "bf16", "f32x3")),
     # odd group counts at lengths whose levels (256 / 128 / 32 / 8) include the short ones (<= 32 rows, a power of two: gn_norm_apply): a group of the skip
     # concat lies across both sources -- the only group (g1s), or the middle one of three (g3s: widths 48 / 96, groups of 16 / 32 channels, 32 / 64 over a concat)
-    "g1s": (_t(16, resnet_groups=1), (2, 512), 41, ("fp32", "bf16")),
-    "g3s": (_t(24, resnet_groups=3, attention_heads=3), (2, 512), 42, ("fp32", "bf16")),
-    "km4": (_t(16, kernel_multiplier_downsample=4), (2, 576), 38, ("fp32", "bf16")),
+    "g1s": (_t(16, resnet_groups=1), (2, 512), 41, ("fp32", "bf16", "f32x3")),
+    "g3s": (_t(24, resnet_groups=3, attention_heads=3), (2, 512), 42, ("fp32", "bf16", "f32x3")),
+    "km4": (_t(16, kernel_multiplier_downsample=4), (2, 576), 38, ("fp32", "bf16", "f32x3")),
     "f83": (_t(16, multipliers=[1, 2, 4], factors=[8, 3], num_blocks=[3, 1], attentions=[True, False], use_skip_scale=False,
-               use_attention_bottleneck=False, attention_multiplier=4, attention_heads=4), (3, 432), 39, ("fp32", "bf16")),
+               use_attention_bottleneck=False, attention_multiplier=4, attention_heads=4), (3, 432), 39, ("fp32", "bf16", "f32x3")),
     "win16": (_t(16, num_filters=32, multipliers=[2, 2, 4], factors=[2, 2], num_blocks=[1, 1], attentions=[False, True], window_length=16,
-                 stride=4, in_channels=2, attention_multiplier=1), (2, 176), 40, ("fp32", "bf16")),
+                 stride=4, in_channels=2, attention_multiplier=1), (2, 176), 40, ("fp32", "bf16", "f32x3")),
 }
+
+
+# The bar of the split-bf16 mode per launch (relative L2 of one teacher-forced tensor against oracle/unet1d.py storage="f32x3", and of the output): half the
+# smallest figure a TRUNCATING hi / lo split leaves on any GEMM-fed tensor of the twelve cases (5.7e-6: g16 mid.post, a conv whose identity residual dilutes
+# it most), ~7x the worst figure of the same three products summed in fp32 (4.2e-7).  Derived from the oracle alone and re-derived by
+# tests/test_oracle_unet1d_x3.py; never fitted to what a device run gives.
+X3_LAUNCH_TOL = 2.8e-6
+
+
+def x3_gemm_fed(cfg: UNet1dConfig, taps) -> list:
+    """The recorded names (plus "out") whose tensor a split-bf16 product of the device writes directly: everything but to_in, the embeddings, the three
+    LayerNorm outputs of a transformer, an ``.att`` of the fp32 vector kernel and an output of the fp32 to_out kernel."""
+    from oracle import unet1d as O
+    fed = []
+    for k, v in taps.items():
+        if k in ("to_in", "temb", "class_emb") or k.endswith((".ln", ".n1", ".n2")):
+            continue
+        if k.endswith(".att") and not O.x3_attention(v.shape[1] // cfg.attention_heads, v.shape[2], v.shape[1]):
+            continue
+        fed.append(k)
+    return fed + (["out"] if O.x3_to_out(cfg.num_filters) else [])
 
 
 def inputs(cfg: UNet1dConfig, shape, seed: int = 0):
@@ -79,6 +100,18 @@ def float64_run(cfg, w, w64, x, t):
     dist = {k: rel(t32[k], t64[k]) for k in t64}
     dist["out"] = rel(y32, y64)
     return y64, t64, dist
+
+
+@functools.lru_cache(maxsize=None)
+def x3_case(cid: str):
+    """The free-running split-bf16 oracle of a sweep case on its own inputs: (float64 output, {name: float64 tensor}), computed once per session."""
+    from oracle import unet1d as O
+    cfg, shape, seed, _ = CASES[cid]
+    x, t = inputs(cfg, shape, seed)
+    taps = {}
+    with torch.no_grad():
+        y = O.unet1d_forward(weights(cid)[1], cfg, x.double(), t.double(), taps=taps, storage="f32x3")
+    return y, taps
 
 
 @functools.lru_cache(maxsize=None)

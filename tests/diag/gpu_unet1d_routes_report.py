@@ -3,7 +3,8 @@ comparison itself is tests/gpu_helpers.py ``sweep_fp32_report`` / ``sweep_bf16_r
 
     ADF_GEMM_TRACE=1 python tests/diag/gpu_unet1d_routes_report.py <route case>        # last stdout line: the report as JSON; stderr: [adf gemm] lines
 
-fp32 / f32x3: the output and every recorded tensor, unsubsampled, against oracle/unet1d.py run in float64 (max |a - b| / max |b|).
+fp32: the output and every recorded tensor, unsubsampled, against oracle/unet1d.py run in float64 (max |a - b| / max |b|).
+f32x3: the same ("free"), and every recorded tensor teacher-forced against the split-bf16 oracle (relative L2; ``sweep_x3_report``).
 bf16: every stored tensor teacher-forced against the bf16-storage oracle (relative L2), the output against the oracle's forced output."""
 import json
 import os
@@ -33,6 +34,9 @@ def _cfg(**kw):
 ROUTE_CASES = {}
 for _dt in ("fp32", "bf16"):
     ROUTE_CASES["ws192_" + _dt] = (_cfg(channels=32, num_filters=32, multipliers=[1, 6, 6, 6], factors=[2, 8, 2], num_blocks=[1, 1, 1]), (16, 8192), 51, _dt)
+ROUTE_CASES["ws192_f32x3"] = ROUTE_CASES["ws192_fp32"][:3] + ("f32x3",)
+for _b in (17, 9):
+    ROUTE_CASES["rbx3_small_b%d_f32x3" % _b] = (_cfg(channels=64, num_filters=64, multipliers=[1, 2, 4], factors=[2, 2], num_blocks=[1, 1]), (_b, 2048), 54, "f32x3")
 ROUTE_CASES["pp384_bf16"] = (_cfg(channels=64, num_filters=64, multipliers=[1, 6], factors=[2], num_blocks=[1]), (44, 512), 52, "bf16")
 ROUTE_CASES["pp128g1_bf16"] = (_cfg(channels=64, num_filters=64, multipliers=[1, 2], factors=[2], num_blocks=[1], resnet_groups=1), (32, 2048), 53, "bf16")
 
@@ -46,6 +50,8 @@ def main():
     net = H.sweep_make(cfg, w, dtype)
     if dtype == "bf16":
         rep = H.sweep_bf16_report(cfg, w, x, t, net)
+    elif dtype == "f32x3":
+        rep = H.sweep_x3_report(cfg, w, {k: v.double() for k, v in w.items()}, x, t, net)
     else:
         rep = H.sweep_fp32_report(cfg, w, {k: v.double() for k, v in w.items()}, x, t, net)
     rep.pop("y"); rep.pop("got")

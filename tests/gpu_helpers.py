@@ -83,6 +83,27 @@ def tap_errors(cfg, x, t, dtype="fp32", flags=0):
     return errs, y.cpu(), y_o
 
 
+def tap_errors_x3(cfg, x, t, flags=0):
+    """``tap_errors`` in the split-bf16 mode plus, from the SAME device run, every recorded tensor teacher-forced against the split-bf16 oracle
+    (storage="f32x3", relative L2; "out" from the device's last tensor).  -> (free-running errors, forced errors)."""
+    net, w = make_net(cfg, "f32x3", flags)
+    y = net(x.cuda(), t.cuda())
+    torch.cuda.synchronize()
+    hd = net.native(torch.device("cuda", torch.cuda.current_device()))
+    dev = {name: hd.tap(name, x.shape[0], y.device).cpu() for name in hd.tap_names()}
+    y = y.cpu()
+    taps_o, forced = {}, {}
+    with torch.no_grad():
+        y_o = O.unet1d_forward(w, cfg, x, t, taps=taps_o)
+        y_f = O.unet1d_forward({k: v.double() for k, v in w.items()}, cfg, x.double(), t.double(), storage="f32x3", force=dev, errs=forced)
+    errs = {name: rel_err(dev[name], taps_o[name]) for name in dev}
+    errs["out"] = rel_err(y, y_o)
+    missing = set(dev) - set(forced)
+    assert not missing, f"device taps the oracle does not record: {missing}"
+    forced["out"] = rel_l2(y, y_f)
+    return errs, forced
+
+
 _C2_LINE = re.compile(r"^\[adf conv2d\] (\S+)\s+B=(\d+) H=(\d+) W=(\d+) cin=(\d+) c0=(\d+) cout=(\d+) taps=(\d+) mode=(\d+) ab=(\d+) act=(\d+) res=(\d+) stats=(\d+)$")
 _C2_KEYS = ("B", "H", "W", "cin", "c0", "cout", "taps", "mode", "ab", "act", "res", "stats")
 
@@ -173,6 +194,35 @@ def sweep_fp32_report(cfg, w, w64, x, t, net, oracle=None):
     assert y.shape == y64.shape
     return {"taps": errs, "names": names, "missing": missing, "out": SW.rel(y, y64) if bool(torch.isfinite(y).all()) else float("inf"),
             "oracle_dist": max(dist.values()), "ref_absmax": min(float(v.abs().max()) for v in t64.values()),
+            "device_seconds": t1 - t0, "oracle_seconds": time.time() - t1, "y": y, "got": got}
+
+
+def sweep_x3_report(cfg, w, w64, x, t, net, oracle=None):
+    """f32x3 device run, ONE run held two ways.  ``taps`` / ``out``: every recorded tensor teacher-forced against the split-bf16 oracle (oracle/unet1d.py
+    storage="f32x3": relative L2 of one launch on the device's own inputs; the output from the device's last tensor), bar SW.X3_LAUNCH_TOL.  ``free`` /
+    ``free_out``: the same tensors free-running against the float64 oracle (max-norm relative), bar F32X3_TOL.  ``oracle``: as in sweep_fp32_report."""
+    t0 = time.time()
+    y, got, names = sweep_device_run(net, x, t)
+    t1 = time.time()
+    y64, t64, dist = oracle if oracle is not None else SW.float64_run(cfg, w, w64, x, t)
+    finite = bool(torch.isfinite(y).all()) and all(bool(torch.isfinite(v).all()) for v in got.values())
+    missing = [k for k in names if k not in t64]
+    free = {}
+    for k in names:
+        if k in t64:
+            assert got[k].shape == t64[k].shape, (k, got[k].shape, t64[k].shape)
+            free[k] = SW.rel(got[k], t64[k]) if finite else float("inf")
+    assert y.shape == y64.shape
+    forced = {}
+    with torch.no_grad():
+        y_f = O.unet1d_forward(w64, cfg, x.double(), t.double(), storage="f32x3", force=got, errs=forced)
+    missing += sorted(set(got) - set(forced))
+    if not finite:
+        forced = {k: float("inf") for k in forced}
+    return {"taps": forced, "names": names, "missing": missing, "out": O.rel_l2(y, y_f) if finite else float("inf"),
+            "free": free, "free_out": SW.rel(y, y64) if finite else float("inf"),
+            "oracle_dist": max(dist.values()), "ref_absmax": min(float(v.abs().max()) for v in t64.values()),
+            "shapes": {k: list(v.shape) for k, v in got.items()},
             "device_seconds": t1 - t0, "oracle_seconds": time.time() - t1, "y": y, "got": got}
 
 

@@ -26,7 +26,10 @@ Tolerances.  north_star: <= 1e-3 relative (fp32) to the reference CPU path.
       was 5-10x larger.)
     The oracle running FREE from the same input is as far from the device as bf16 is from fp32 (the rounding realisations
     decorrelate within a few layers: measured 1.0e-2 .. 1.5e-2 at the end of the net, profiles/r02_bf16_parity_report.json),
-    so that comparison is held to BF16_TOL like bf16-vs-fp32 and adds nothing beyond it; the teacher-forced one is the test."""
+    so that comparison is held to BF16_TOL like bf16-vs-fp32 and adds nothing beyond it; the teacher-forced one is the test.
+  * split-bf16 mode (compute_dtype="f32x3") is held free-running to F32X3_TOL (max norm, against the fp32 oracle) and, from the same device run, teacher-forced per
+    recorded tensor against the split-bf16 oracle (oracle/unet1d.py storage="f32x3": the device's own hi / lo split of every operand of every split product, float64
+    accumulation) at X3_LAUNCH_TOL = 2.8e-6 relative L2, a bar derived on the CPU (tests/test_oracle_unet1d_x3.py): measured <= 1.1e-6 on the presets."""
 import ctypes as C
 import os
 
@@ -37,7 +40,8 @@ import torch
 import audiodiffuser_amd as A
 from audiodiffuser_amd import _lib
 from audiodiffuser_amd.weights import generate_noise, generate_weights
-from gpu_helpers import assert_gemm_route_trace, make_net, rel_err, rel_l2, tap_errors, tap_errors_bf16, golden_inputs
+from gpu_helpers import assert_gemm_route_trace, make_net, rel_err, rel_l2, tap_errors, tap_errors_bf16, tap_errors_x3, golden_inputs
+from oracle.unet1d_sweep import X3_LAUNCH_TOL
 
 pytestmark = pytest.mark.gpu
 FP32_TOL = 1e-3       # the north-star bar; measured ~2e-6
@@ -69,32 +73,44 @@ def test_every_layer_fp32(tag, mk, flags):
 
 
 F32X3_TOL = 2e-4      # split-bf16 mode per recorded tensor, free-running, max-norm relative (operands carry 16 mantissa bits: ~1e-5 per layer)
+# The mode's sharp bar is X3_LAUNCH_TOL (oracle/unet1d_sweep.py, derived in tests/test_oracle_unet1d_x3.py): every recorded tensor of the same device run
+# teacher-forced against the split-bf16 oracle (oracle/unet1d.py storage="f32x3"), relative L2 -- one launch on the device's own inputs, ~70x tighter.
+
+
+def _assert_x3_forced(forced, tag):
+    worst = max(forced, key=forced.get)
+    print(f"{tag} f32x3 forced: tensors {len(forced)} worst {worst} {forced[worst]:.3e} out {forced['out']:.3e}")
+    bad = {k: v for k, v in forced.items() if not v < X3_LAUNCH_TOL}
+    assert len(forced) > 10 and not bad, sorted(bad.items(), key=lambda kv: -kv[1])[:8]
 
 
 @pytest.mark.parametrize("tag,mk", CASES + [("c3short", A.config_c3)])
 def test_every_layer_f32x3(tag, mk):
     """ADF_DTYPE_F32X3 (fp32 storage, every GEMM operand split into bf16 hi + lo, three bf16 MFMAs per product): every recorded tensor of the net
     against the fp32 oracle, free-running.  Routes at these sizes: the generic implicit-GEMM kernel and the split-K kernel (the resblock kernel of the long
-    levels, adf_gemm_rbx3.h, has its own test below)."""
+    levels, adf_gemm_rbx3.h, has its own test below).  The same run teacher-forced against the split-bf16 oracle at X3_LAUNCH_TOL: measured worst
+    1.0e-6 (tiny up0.block0.h1) / 1.0e-6 (c1 down4.block0.h1) / 1.1e-6 (c3short up0.block2.h1), outputs 8.4e-8 .. 9.0e-8."""
     if tag == "c3short":
         x, t = generate_noise(5, 2, 4096) * 0.7, torch.tensor([-0.6, 0.4])
     else:
         x, t = golden_inputs(tag)
-    errs, y, yo = tap_errors(mk(), x, t, "f32x3", 0)
+    errs, forced = tap_errors_x3(mk(), x, t)
     assert len(errs) > 10
     bad = {k: v for k, v in errs.items() if not v < F32X3_TOL}
     assert not bad, bad
     assert max(errs.values()) > 1e-7          # (not silently the exact-fp32 route)
+    _assert_x3_forced(forced, tag)
 
 
 @pytest.mark.parametrize("preset", ["c2", "c3"])
 def test_split_bf16_resblock_dma_kernel_on_small_batches_every_tensor_vs_fp32_oracle(preset):
     """adf_gemm_rbx3.h (the resblock conv kernel's data path on fp32 storage: 32-channel K blocks split into bf16 hi + lo in the MFMA gaps, three MFMAs
-    per product) on every shape it is written for: ADF_GEMM_RBX3=2 lets it take the resblock convs at batch 8, where the L = 256 level runs its
-    128-row form -- incl. the raw folded down conv, the f = 2 transposed convs in their 3-tap form, the identity-residual conv2, the 1x1-residual K
+    per product): ADF_GEMM_RBX3=2 lets it take the resblock convs at batch 8 (its 256-row form: the recorded trace shows the L = 256 level on the split-K kernel,
+    which is asked first; the 128-row form runs in tests/test_unet1d_sweep_gpu.py, route case rbx3_small) -- incl. the raw folded down conv, the f = 2 transposed convs in their 3-tap form, the identity-residual conv2, the 1x1-residual K
     segment and the two-source concat of the up path.
     BASELINE configs[1] net (and the configs[2] net: the same widths with attention from the 1024-token level on, i.e. the K-from-global attention
-    kernel between the kernel's launches), every recorded tensor free-running against the fp32 oracle at the mode's bound."""
+    kernel between the kernel's launches), every recorded tensor free-running against the fp32 oracle at the mode's bound, and teacher-forced against the
+    split-bf16 oracle at X3_LAUNCH_TOL (measured worst 8.1e-7 / 8.5e-7, both conv1 outputs; output 9.0e-8 / 8.5e-8)."""
     import json
     import subprocess
     import sys
@@ -116,6 +132,8 @@ def test_split_bf16_resblock_dma_kernel_on_small_batches_every_tensor_vs_fp32_or
         assert {"down3.conv", "down3.block0.h1", "down3.block1", "up2.block0.h1", "up2.block2"} <= set(errs)
     bad = {k: v for k, v in errs.items() if not v < F32X3_TOL}
     assert not bad, bad
+    assert set(rep["forced_x3"]) == set(errs)
+    _assert_x3_forced(rep["forced_x3"], preset + " rbx3")
 
 
 def _assert_bf16_parity(cfg, x, t, chained=True, flags=0):
@@ -547,26 +565,30 @@ def test_config3_bf16_attention_at_1024_tokens_vs_bf16_oracle():
 def test_config3_bf16_attention_at_token_counts_that_do_not_fill_the_workgroups():
     """The MFMA attention kernel shares one (sample, head) pair's V^T among the 8 / 4 / 2 / 1 waves of a workgroup and hands them query tiles in groups: at
     L = 5120 the C3 net attends over 320 / 80 / 20 / 5 / 5 tokens -- ten query tiles on eight-wave workgroups (a second group with six idle waves), three on
-    two-wave ones, and key counts that are no multiple of the 32-key tile -- every stored tensor against the bf16-storage oracle, fp32 against the oracle."""
+    two-wave ones, and key counts that are no multiple of the 32-key tile -- every stored tensor against the bf16-storage oracle, fp32 against the oracle; the
+    f32x3 run also teacher-forced against the split-bf16 oracle (measured worst down5.block0.h1 8.2e-7, output 8.4e-8)."""
     x, t = generate_noise(11, 2, 5120) * 0.7, torch.tensor([-0.7, 0.3])
     forced, chain = _assert_bf16_parity(A.config_c3(), x, t)
     assert "down2.attn" in forced and "up3.attn" in forced
     errs, _, _ = tap_errors(A.config_c3(), x, t, "fp32", 0)
     bad = {k: v for k, v in errs.items() if not v < FP32_TIGHT}
     assert not bad, bad
-    errs, _, _ = tap_errors(A.config_c3(), x, t, "f32x3", 0)      # 320 tokens: the split-bf16 attention kernel's K-from-global form on eight waves
+    errs, forced = tap_errors_x3(A.config_c3(), x, t)      # 320 tokens: the split-bf16 attention kernel's K-from-global form on eight waves
     bad = {k: v for k, v in errs.items() if not v < F32X3_TOL}
     assert not bad, bad
+    _assert_x3_forced(forced, "c3 at 5120")
 
 
 def test_config3_f32x3_attention_at_1024_tokens_vs_oracle():
     """BASELINE config 3 in the split-bf16 mode at full length: ``attention_x3_kernel<8, true>`` (K rows from global memory split in registers, one pair's
-    V^T hi | lo = 132 KB of LDS shared by eight waves) at N = 1024 tokens, every recorded tensor against the fp32 oracle."""
-    errs, _, _ = tap_errors(A.config_c3(), generate_noise(3, 1, 16384) * 0.6, torch.tensor([0.2]), "f32x3", 0)
+    V^T hi | lo = 132 KB of LDS shared by eight waves) at N = 1024 tokens, every recorded tensor against the fp32 oracle, and teacher-forced against the
+    split-bf16 oracle (measured worst up1.block1.h1 7.6e-7, output 8.6e-8)."""
+    errs, forced = tap_errors_x3(A.config_c3(), generate_noise(3, 1, 16384) * 0.6, torch.tensor([0.2]))
     assert "down2.attn" in errs and "up3.attn" in errs
     bad = {k: v for k, v in errs.items() if not v < F32X3_TOL}
     assert not bad, bad
     assert max(errs.values()) > 1e-7
+    _assert_x3_forced(forced, "c3 at 16384")
 
 
 def test_config3_dpm_sampler_full_length_vs_oracle():
