@@ -151,6 +151,10 @@ EXPORTS = {
     "adf_istft_basis": (C.c_int, [C.POINTER(AdfIstftConfig), C.c_void_p, C.c_void_p, C.c_void_p]),
     "adf_istft_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "adf_istft_destroy": (None, [C.c_void_p]),
+    "adf_stft_create": (C.c_int, [C.POINTER(AdfIstftConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "adf_stft_basis": (C.c_int, [C.POINTER(AdfIstftConfig), C.c_void_p, C.c_void_p]),
+    "adf_stft_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p]),
+    "adf_stft_destroy": (None, [C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

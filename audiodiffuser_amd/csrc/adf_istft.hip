@@ -2,7 +2,7 @@
 // Replaces, after the sampler, src/models/diffunet_complex_module.py:90-99 (permute + view_as_complex, spec_back of src/models/utils.py:22-28,
 // torch.istft with center=True and length=None).
 #include "adf_istft.h"
-#include "adf_api_internal.h"
+#include "adf_spectral_host.h"
 
 #include <cmath>
 #include <string>
@@ -182,8 +182,6 @@ hipError_t launch_istft(const IstftArgs& a, hipStream_t s) {
 // =====================================================================================================
 // host: argument checks, the tables, the plan
 // =====================================================================================================
-using adf_api::g_create_error;
-
 struct adf_istft_plan {
     int device = 0;
     int n_fft = 0, h = 0, F = 0, Fp = 0, D = 0;
@@ -195,30 +193,18 @@ struct adf_istft_plan {
 
 namespace {
 
-int istft_fail(const std::string& m) { g_create_error = m; return 1; }
+using adf_spectral::window_f64;
+typedef adf_spectral::DeviceScope IstftDeviceScope;
 
-// The window in double: the caller's n_fft floats, or the periodic Hann window.
-std::vector<double> istft_window(const adf_istft_config& c, const float* window) {
-    std::vector<double> w(c.n_fft);
-    for (int m = 0; m < c.n_fft; ++m) w[m] = window ? (double)window[m] : 0.5 - 0.5 * std::cos(2.0 * M_PI * m / c.n_fft);
-    return w;
-}
+int istft_fail(const std::string& m) { return adf_spectral::fail(m); }
 
 int istft_check(const char* fn, const adf_istft_config* cfg, const float* window) {
+    if (adf_spectral::check_config(fn, cfg, "with center=False a Hann window fails torch.istft's own envelope check")) return 1;
     const std::string f = std::string(fn) + ": ";
-    if (!cfg) return istft_fail(f + "null config");
     const adf_istft_config& c = *cfg;
-    if (c.n_fft < 32 || c.n_fft > 1024 || c.n_fft % 2) return istft_fail(f + "n_fft must be even and in [32, 1024], got " + std::to_string(c.n_fft));
-    if (c.hop_length < 32 || c.hop_length > 256 || c.hop_length % 32)
-        return istft_fail(f + "hop_length must be a multiple of 32 in [32, 256], got " + std::to_string(c.hop_length));
-    if ((c.n_fft + c.hop_length - 1) / c.hop_length > adf::kIstftMaxD)
-        return istft_fail(f + "hop_length " + std::to_string(c.hop_length) + " is too small for n_fft " + std::to_string(c.n_fft) + ": ceil(n_fft / hop_length) must be at most 8");
-    if (!c.center) return istft_fail(f + "center must be true (with center=False a Hann window fails torch.istft's own envelope check)");
-    if (!(c.spec_abs_exponent > 0.0) || !std::isfinite(c.spec_abs_exponent)) return istft_fail(f + "spec_abs_exponent must be > 0");
-    if (!(c.spec_factor > 0.0) || !std::isfinite(c.spec_factor)) return istft_fail(f + "spec_factor must be > 0");
     // torch.istft's NOLA check: the overlap-added squared window over the kept samples.  Two frames (every kept sample of any T >= 2 is covered by
     // at least the pair of frames checked here, and squares only add) and the steady state.
-    const std::vector<double> w = istft_window(c, window);
+    const std::vector<double> w = window_f64(c, window);
     const int N = c.n_fft, h = c.hop_length, D = (N + h - 1) / h;
     auto wsq = [&](int off) { return off >= 0 && off < N ? w[off] * w[off] : 0.0; };
     double worst = 1e300;
@@ -235,7 +221,7 @@ int istft_check(const char* fn, const adf_istft_config* cfg, const float* window
 // basis [2][D h][F] and wsq [D h] (include/audiodiffuser_amd.h); either may be null.
 void istft_tables(const adf_istft_config& c, const float* window, float* basis, float* wsq) {
     const int N = c.n_fft, h = c.hop_length, F = N / 2 + 1, D = (N + h - 1) / h, M = D * h;
-    const std::vector<double> w = istft_window(c, window);
+    const std::vector<double> w = window_f64(c, window);
     const double s = c.normalized ? std::sqrt((double)N) / N : 1.0 / N;
     if (wsq)
         for (int m = 0; m < M; ++m) wsq[m] = m < N ? (float)(w[m] * w[m]) : 0.f;
@@ -255,20 +241,6 @@ void istft_tables(const adf_istft_config& c, const float* window, float* basis, 
             S[(size_t)m * F + k] = sv;
         }
 }
-
-struct IstftDeviceScope {
-    int prev = -1;
-    bool ok = true;
-    explicit IstftDeviceScope(int device) {
-        int cur = -1;
-        if (hipGetDevice(&cur) != hipSuccess) { ok = false; return; }
-        if (cur != device) {
-            if (hipSetDevice(device) != hipSuccess) { ok = false; return; }
-            prev = cur;
-        }
-    }
-    ~IstftDeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 }  // namespace
 

@@ -1,4 +1,5 @@
-"""``SpecToWave``: the sampled complex spectrogram to audio on the device, in one HIP launch (csrc/adf_istft.hip).
+"""``SpecToWave``: the sampled complex spectrogram to audio on the device, in one HIP launch (csrc/adf_istft.hip), and ``WaveToSpec``, the way
+back: a waveform to the ``[B, 2, F, T]`` spectrogram the networks take, in one HIP launch (csrc/adf_stft.hip).
 
 Replaces the tail of the reference's ``DiffUnetComplexModule.synthesize_from_noise`` (src/models/diffunet_complex_module.py:90-99)::
 
@@ -6,7 +7,14 @@ Replaces the tail of the reference's ``DiffUnetComplexModule.synthesize_from_noi
     spec  = spec_back(spec, spec_abs_exponent, spec_factor)                       # src/models/utils.py:22-28
     audio = torch.istft(spec, window=hann(n_fft), normalized=True, n_fft=n_fft, hop_length=hop_length, center=True)
 
-It takes the sampler's ``[B, 2, F, T]`` tensor as it is -- the permute and the complex view are never materialised.  There is no CPU fallback.
+It takes the sampler's ``[B, 2, F, T]`` tensor as it is -- the permute and the complex view are never materialised.  ``WaveToSpec`` replaces the
+head of ``DiffUnetComplexModule.forward`` (src/models/diffunet_complex_module.py:109-115)::
+
+    spec = torch.stft(audio, window=hann(n_fft), normalized=True, return_complex=True, n_fft=n_fft, hop_length=hop_length, center=True)
+    spec = spec_fwd(spec, spec_abs_exponent, spec_factor).unsqueeze(1)            # src/models/utils.py:8-19
+    spec = torch.cat((spec.real, spec.imag), dim=1)
+
+Neither the reflect-padded audio nor the complex spectrogram is materialised.  There is no CPU fallback in either direction.
 """
 from __future__ import annotations
 
@@ -121,5 +129,89 @@ class SpecToWave(nn.Module):
         for plan in getattr(self, "_plans", {}).values():
             try:
                 self._lib.adf_istft_destroy(plan)
+            except Exception:
+                pass
+
+
+def stft_basis(n_fft: int = 510, hop_length: int = 128, center: bool = True, normalized: bool = True, window=None,
+               spec_abs_exponent: float = 0.2, spec_factor: float = 0.6) -> np.ndarray:
+    """The host table a ``WaveToSpec`` plan is built from (``adf_stft_basis``; no device is touched): fp32 ``[2, F, n_fft]``, the windowed and
+    scaled cosine rows, then the negated sine rows."""
+    lib = _lib.load_library()
+    cfg = _config(n_fft, hop_length, spec_abs_exponent, spec_factor, center, normalized)
+    w = _host_window(window, n_fft)
+    wp = w.ctypes.data_as(C.c_void_p) if w is not None else None
+    _checked(lib, lib.adf_stft_basis(C.byref(cfg), wp, None))
+    basis = np.empty((2, cfg.n_fft // 2 + 1, cfg.n_fft), dtype=np.float32)
+    _checked(lib, lib.adf_stft_basis(C.byref(cfg), wp, basis.ctypes.data_as(C.c_void_p)))
+    return basis
+
+
+class WaveToSpec(nn.Module):
+    """``forward(audio [B, L] fp32) -> [B, 2, n_fft / 2 + 1, 1 + L // hop_length] fp32`` on the same ROCm device: channel 0 real, 1 imaginary.
+
+    The mirror of ``SpecToWave``, a module without parameters (hydra ``_target_: audiodiffuser_amd.WaveToSpec``).  ``window``: a 1-D tensor of
+    ``n_fft`` values, or None for ``torch.hann_window(n_fft)``.  ``L`` must exceed ``n_fft / 2`` (the reflect padding) and need not be a multiple of
+    anything; samples that no frame reaches are ignored, as in ``torch.stft``."""
+
+    def __init__(self, n_fft: int = 510, hop_length: int = 128, spec_abs_exponent: float = 0.2, spec_factor: float = 0.6,
+                 center: bool = True, normalized: bool = True, window=None):
+        super().__init__()
+        self.n_fft, self.hop_length = int(n_fft), int(hop_length)
+        self.spec_abs_exponent, self.spec_factor = float(spec_abs_exponent), float(spec_factor)
+        self.center, self.normalized = bool(center), bool(normalized)
+        self._window = _host_window(window, n_fft)
+        self._lib = _lib.load_library()
+        self._cfg = _config(n_fft, hop_length, spec_abs_exponent, spec_factor, center, normalized)
+        _checked(self._lib, self._lib.adf_stft_basis(C.byref(self._cfg), self._window_ptr(), None))    # argument checks only
+        self._plans = {}                   # device index -> adf_stft_plan*
+
+    def _window_ptr(self):
+        return self._window.ctypes.data_as(C.c_void_p) if self._window is not None else None
+
+    def _plan(self, device: torch.device) -> C.c_void_p:
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        plan = self._plans.get(idx)
+        if plan is None:
+            plan = C.c_void_p()
+            with torch.cuda.device(idx):   # a plan belongs to the device current at its creation
+                rc = self._lib.adf_stft_create(C.byref(self._cfg), self._window_ptr(), C.byref(plan))
+            if rc != 0:
+                msg = self._lib.adf_last_error(None)
+                raise _lib.AdfError(f"adf_stft_create: {msg.decode() if msg else 'unknown error'}")
+            self._plans[idx] = plan
+        return plan
+
+    def forward(self, audio: torch.Tensor) -> torch.Tensor:
+        x = audio
+        if not torch.is_tensor(x) or x.dim() != 2:
+            raise ValueError(f"WaveToSpec takes audio [B, L], got {tuple(x.shape) if torch.is_tensor(x) else type(x)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"WaveToSpec takes an fp32 tensor, got {x.dtype}")
+        if not x.is_contiguous():
+            raise ValueError("WaveToSpec takes a contiguous [B, L] tensor")
+        B, L = int(x.shape[0]), int(x.shape[1])
+        if B < 1 or L <= self.n_fft // 2:
+            raise ValueError(f"WaveToSpec needs B >= 1 and audio longer than n_fft / 2 = {self.n_fft // 2} samples (the reflect padding), "
+                             f"got B = {B}, L = {L}")
+        if not x.is_cuda:
+            raise RuntimeError("the HIP WaveToSpec only runs on a ROCm device ('cuda'); there is no CPU fallback")
+        T = 1 + L // self.hop_length
+        out = torch.empty((B, 2, self.n_fft // 2 + 1, T), device=x.device, dtype=torch.float32)
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        rc = self._lib.adf_stft_run(self._plan(x.device), x.data_ptr(), B, L, out.data_ptr(), T, stream)
+        if rc != 0:
+            msg = self._lib.adf_last_error(None)
+            raise _lib.AdfError(f"adf_stft_run: {msg.decode() if msg else 'unknown error'}")
+        return out
+
+    def extra_repr(self) -> str:
+        return (f"n_fft={self.n_fft}, hop_length={self.hop_length}, spec_abs_exponent={self.spec_abs_exponent}, spec_factor={self.spec_factor}, "
+                f"normalized={self.normalized}")
+
+    def __del__(self):
+        for plan in getattr(self, "_plans", {}).values():
+            try:
+                self._lib.adf_stft_destroy(plan)
             except Exception:
                 pass

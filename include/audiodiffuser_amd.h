@@ -52,7 +52,8 @@ extern "C" {
  * 7: adf_set_preconditioning (ADF_PRECOND_EDM / VE / VP / V_EDM) and adf_debug_coef_rows.  The preconditioning kind travels as handle state, in the
  *    style of adf_set_dynamic_threshold: adf_sampler_desc and the argument list of adf_denoise are unchanged, so a caller that fills only the
  *    fields of version 6 and never calls the setter still gets EluDiffusion's rows.
- *    Added without a bump (new symbols only, nothing of the above changes): adf_istft_config and the four adf_istft_* entry points. */
+ *    Added without a bump (new symbols only, nothing of the above changes): adf_istft_config and the four adf_istft_* entry points;
+ *    the four adf_stft_* entry points (WaveToSpec), which take the same adf_istft_config. */
 #define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
@@ -297,6 +298,30 @@ int adf_istft_create(const adf_istft_config* cfg, const float* window, adf_istft
 int adf_istft_basis(const adf_istft_config* cfg, const float* window, float* basis, float* wsq);
 int adf_istft_run(adf_istft_plan* plan, const float* spec, int B, int T, float* audio, int64_t audio_len, void* stream);
 void adf_istft_destroy(adf_istft_plan* plan);
+
+/* WaveToSpec: the head of DiffUnetComplexModule.forward (src/models/diffunet_complex_module.py:109-115) in one launch --
+ * torch.stft(window, normalized, center=True, pad_mode="reflect", return_complex=True) + spec_fwd (src/models/utils.py:8-19) + cat(real, imag).
+ * audio is fp32 [B][L], rows back to back and only 4-byte aligned (any L > n_fft / 2: torch refuses a shorter row for the reflect padding, so does
+ * adf_stft_run); spec is fp32 [B][2][n_fft / 2 + 1][T] with T = 1 + L / hop_length, channel 0 real, 1 imaginary -- the tensor the networks and
+ * adf_istft_run take.  Samples no frame reaches are ignored.  The padding is never materialised; the windowed DFT is one exact-fp32 MFMA GEMM against
+ * a cosine / sine basis built in double on the host, and spec_fwd runs on its accumulators.  A bin whose magnitude is exactly 0 gives 0.
+ *   The accepted arguments are those of adf_istft_*: n_fft even in [32, 1024]; hop_length a multiple of 32 in [32, 256];
+ *   ceil(n_fft / hop_length) <= 8; center must be 1; spec_abs_exponent > 0, spec_factor > 0.  window: n_fft floats on the HOST, or NULL for the
+ *   periodic Hann window; there is no overlap-add condition in this direction, but a window that is zero everywhere (or not finite) is refused.
+ *   adf_stft_run refuses L <= n_fft / 2, L >= 2^30, T != 1 + L / hop_length and B outside [1, 65535].
+ * Arguments are checked before any device is looked for.  A plan belongs to the device current at adf_stft_create; adf_stft_run makes it current,
+ * enqueues on `stream`, and neither allocates nor synchronises.  Every function returns 0 on success; adf_last_error(NULL) gives the message of the
+ * last failure, which starts with the function's name and names the argument. */
+typedef struct adf_stft_plan adf_stft_plan;
+int adf_stft_create(const adf_istft_config* cfg, const float* window, adf_stft_plan** out);
+/* Host only (touches no device): the table the plan is built from, with F = n_fft / 2 + 1 and s = n_fft^-1/2 when normalized, else 1:
+ *   basis [2][F][n_fft]:  basis[0][k][m] = w[m] cos(2 pi m k / n_fft) s,  basis[1][k][m] = -w[m] sin(2 pi m k / n_fft) s, with the rows
+ *                         basis[1][0] and basis[1][F-1] exactly zero; computed in double, rounded once
+ * basis may be NULL (the arguments are checked and nothing is written).  adf_istft_basis has a second table (the squared window of its overlap-add
+ * envelope); nothing in this direction needs one, so there is no second output here. */
+int adf_stft_basis(const adf_istft_config* cfg, const float* window, float* basis);
+int adf_stft_run(adf_stft_plan* plan, const float* audio, int B, int64_t L, float* spec, int T, void* stream);
+void adf_stft_destroy(adf_stft_plan* plan);
 
 #ifdef __cplusplus
 }
