@@ -469,6 +469,23 @@ int adf_debug_tap_copy(adf_handle* h, const char* name, float* out, void* stream
     return fail(h, std::string("unknown tap ") + name);
 }
 
+int adf_debug_tap_stats(adf_handle* h, const char* name, double* out_host, int* groups, void* stream) {
+    ADF_ON_DEVICE(h);
+    if (!h->last_plan || h->last_plan->dry) return fail(h, "no forward has run yet");
+    const int G = h->net->dims.stat_groups;
+    for (const auto& t : h->last_plan->taps)
+        if (t.name == name) {
+            if (!t.stats) return fail(h, std::string("adf_debug_tap_stats: no statistics were reduced with ") + name);
+            if (groups) *groups = G;
+            if (!out_host) return 0;
+            if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess ||
+                hipMemcpy(out_host, t.stats, (size_t)h->last_plan->B * G * 2 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
+                return fail(h, "adf_debug_tap_stats: copy failed");
+            return 0;
+        }
+    return fail(h, std::string("unknown tap ") + name);
+}
+
 int64_t adf_device_bytes(const adf_handle* h) { return h->bytes; }
 
 }  // extern "C"

@@ -57,7 +57,7 @@ struct Slot {
 };
 
 struct Act { void* p = nullptr; int C = 0, L = 0; double* stats = nullptr; };
-struct TapRec { std::string name; void* p; int C, L; int f32 = 0; float scale = 1.0f; };   // f32: an fp32 buffer whatever the storage mode
+struct TapRec { std::string name; void* p; int C, L; int f32 = 0; float scale = 1.0f; const double* stats = nullptr; };   // f32: an fp32 buffer whatever the storage mode; stats: the GroupNorm statistics reduced with it, if any
 struct RbRec { std::string name; GemmArgs g1, g2; int cin, cout, L; };
 
 struct Plan {
@@ -314,7 +314,7 @@ struct Walker {
         return (double*)(p->stats + off);
     }
     Act new_act(int C, int L) { Act a; a.C = C; a.L = L; a.p = alloc((size_t)p->B * L * C * h->esz); return a; }
-    void tap(const std::string& name, const Act& a) { p->taps.push_back({name, a.p, a.C, a.L}); }
+    void tap(const std::string& name, const Act& a) { p->taps.push_back({name, a.p, a.C, a.L, 0, 1.0f, a.stats}); }
     bool live() const { return !p->dry && !bad; }
 };
 

@@ -25,6 +25,13 @@ extern "C" int adf_debug_rb_timeline(unsigned* out) {
 }
 #endif
 
+#ifdef ADF_UP_TL
+namespace adf { __device__ unsigned long long adf_up_tl[2 * 8 * kUpTlWave]; }
+extern "C" int adf_debug_up_timeline(unsigned long long* out) {
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(adf::adf_up_tl), sizeof(unsigned long long) * 2 * 8 * adf::kUpTlWave);
+}
+#endif
+
 namespace adf {
 
 namespace {
@@ -66,27 +73,27 @@ const char* launch_ws_variant(const GemmArgs& a, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? nullptr : "conv_gemm_ws: launch failed";
 }
 
-// Transposed-conv kernel (adf_gemm_up.h): persistent 512-thread workgroups over tiles of m = 0 .. L
+// Transposed-conv kernel (adf_gemm_up.h): persistent 512-thread workgroups over tiles of the output blocks j = 0 .. L - 1 (a.lin of them per
+// sample; a.mrows = L + 1 is the row count of the m-indexed form the route decision and the trace line speak of)
 template <int CIN, int COUT, int F, int MTP>
-const char* launch_up_mt(const GemmArgs& a, hipStream_t stream) {
+const char* launch_up_mt(const GemmArgs& a, const UpTilePlan& tp, hipStream_t stream) {
     typedef UpCfg<CIN, COUT, F, MTP> Cfg;
     if (!raise_lds_limit<160 * 1024, conv_gemm_up_kernel<CIN, COUT, F, MTP>>()) return "hipFuncSetAttribute(MaxDynamicSharedMemorySize, up) failed";
     static_assert(Cfg::kLds <= 160 * 1024, "up kernel LDS budget");
-    const int tps = (a.mrows + Cfg::TM - 1) / Cfg::TM;
-    const long long items = (long long)a.B * tps * Cfg::NPASS;
-    if (items <= 0 || items > 0x7fffffffLL) return "conv_gemm_up: bad tile count";
-    const long long grid = items < 256 ? items : 256;
-    hipLaunchKernelGGL((conv_gemm_up_kernel<CIN, COUT, F, MTP>), dim3((unsigned)grid), dim3(512), Cfg::kLds, stream, a, (int)items, tps);
+    if (tp.tile_rows != Cfg::TM || tp.items <= 0 || tp.items > 0x7fffffffLL) return "conv_gemm_up: bad tile count";
+    const long long grid = tp.items < kUpGrid ? tp.items : kUpGrid;
+    hipLaunchKernelGGL((conv_gemm_up_kernel<CIN, COUT, F, MTP>), dim3((unsigned)grid), dim3(512), Cfg::kLds, stream, a, (int)tp.items, tp.tiles_per_sample);
     return hipGetLastError() == hipSuccess ? nullptr : "conv_gemm_up: launch failed";
 }
-// tile height: the one that needs fewer rounds of 256 workgroups; ties go to the taller tile (weights are re-read per tile)
+// tile height: up_tile_plan (adf_gemm_up.h)
 template <int CIN, int COUT, int F>
 const char* launch_up(const GemmArgs& a, hipStream_t stream) {
-    auto rounds = [&](int tm, int npass) { return ((long long)a.B * ((a.mrows + tm - 1) / tm) * npass + 255) / 256; };
-    typedef UpCfg<CIN, COUT, F, 2> C2;
-    typedef UpCfg<CIN, COUT, F, 4> C4;
-    if (rounds(C4::TM, C4::NPASS) <= rounds(C2::TM, C2::NPASS)) return launch_up_mt<CIN, COUT, F, 4>(a, stream);
-    return launch_up_mt<CIN, COUT, F, 2>(a, stream);
+    typedef UpCfg<CIN, COUT, F, 1> C1;
+    if (a.lin < 1) return "conv_gemm_up: bad tile count";
+    const UpTilePlan tp = up_tile_plan(a.B, a.lin, C1::WROWS, C1::NPASS);
+    if (tp.mt == 1) return launch_up_mt<CIN, COUT, F, 1>(a, tp, stream);
+    if (tp.mt == 2) return launch_up_mt<CIN, COUT, F, 2>(a, tp, stream);
+    return launch_up_mt<CIN, COUT, F, 4>(a, tp, stream);
 }
 
 // Persistent LDS-DMA kernel (adf_gemm_pp.h): one 512-thread block per CU, block tile (128 MT) x 128.
@@ -470,7 +477,8 @@ GemmPlan decide_conv_gemm(const GemmArgs& a, int dtype) {
             !gn_pending && !g0.act && g0.scale1 == 1.0f && g0.wfrag && g0.c1 == 0 && a.n == f * cout && a.n == a.n_pad && a.mrows == a.lin + 1 &&
             a.out_rows == a.lin * f && a.scatter_pad == f / 2 && a.bias_mod == cout && !a.res && !a.gelu && !a.bias1 &&
             (!a.stats || a.stats_groups == 8)) {
-            // measured (us per launch, this kernel vs the plain / weight-stationary route): 256 -> 256 x4 at L = 16 / 64 / 256: 28 each vs
+            // measured (us per launch at batch 64, this kernel vs the plain / weight-stationary route): 256 -> 256 x4 at L = 16 / 64 / 256: 10.3 / 13.2 /
+            // 32.7 (indexed by output block on 32- / 64- / 128-row tiles; 17.7 / 18.5 / 50.3 over m = 0 .. L on 128-row tiles: profiles/README.md) vs
             // 17 / 27 / 65; 256 -> 128 x2 at L = 1024: 47 vs 66; 128 -> 128 x2 at L = 2048 and 128 -> 64 x2 at L = 4096: 57 / 53 vs 57 / 53
             // (their tiles are bound by the per-CU HBM fetch rate, which this kernel does not overlap with the MFMAs): those two
             // stay on the old routes unless ADF_GEMM_UP=2
@@ -612,3 +620,20 @@ const char* launch_conv_gemm(const GemmArgs& a_in, int dtype, hipStream_t stream
 }
 
 }  // namespace adf
+
+// include/audiodiffuser_amd.h: the tile plan launch_up would take for one of the four shapes of the transposed-conv kernel (host arithmetic only)
+extern "C" int adf_debug_up_tile_plan(int cin, int cout, int f, int B, int L, int* tile_rows, int* items, int* rounds, int* dead_rows) {
+    using namespace adf;
+    if (B < 1 || L < 1 || (long long)B * L > 0x3fffffffLL) return 1;
+    UpTilePlan tp;
+    if (cin == 256 && cout == 256 && f == 4) tp = up_tile_plan(B, L, UpCfg<256, 256, 4, 1>::WROWS, UpCfg<256, 256, 4, 1>::NPASS);
+    else if (cin == 256 && cout == 128 && f == 2) tp = up_tile_plan(B, L, UpCfg<256, 128, 2, 1>::WROWS, UpCfg<256, 128, 2, 1>::NPASS);
+    else if (cin == 128 && cout == 128 && f == 2) tp = up_tile_plan(B, L, UpCfg<128, 128, 2, 1>::WROWS, UpCfg<128, 128, 2, 1>::NPASS);
+    else if (cin == 128 && cout == 64 && f == 2) tp = up_tile_plan(B, L, UpCfg<128, 64, 2, 1>::WROWS, UpCfg<128, 64, 2, 1>::NPASS);
+    else return 1;
+    if (tile_rows) *tile_rows = tp.tile_rows;
+    if (items) *items = (int)tp.items;
+    if (rounds) *rounds = (int)tp.rounds;
+    if (dead_rows) *dead_rows = tp.dead_rows;
+    return 0;
+}

@@ -191,6 +191,15 @@ class NativeHandle:
                    "adf_debug_tap_copy")
         return out
 
+    def tap_stats(self, name: str, batch: int, device: torch.device) -> torch.Tensor:
+        """The GroupNorm statistics reduced with tap ``name`` by the launch that stored it: float64 [batch][groups][2] (sum, sum of squares)."""
+        g = C.c_int()
+        self.check(self.lib.adf_debug_tap_stats(self.h, name.encode(), None, C.byref(g), C.c_void_p(_stream_ptr(device))), "adf_debug_tap_stats")
+        out = torch.empty((batch, g.value, 2), dtype=torch.float64)
+        self.check(self.lib.adf_debug_tap_stats(self.h, name.encode(), C.c_void_p(out.data_ptr()), C.byref(g), C.c_void_p(_stream_ptr(device))),
+                   "adf_debug_tap_stats")
+        return out
+
 
 def _init_like_reference(name: str, shape, kind: str) -> torch.Tensor:
     """Default initialisation equivalent to the reference's torch defaults."""

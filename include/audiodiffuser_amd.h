@@ -53,7 +53,7 @@ extern "C" {
  *    style of adf_set_dynamic_threshold: adf_sampler_desc and the argument list of adf_denoise are unchanged, so a caller that fills only the
  *    fields of version 6 and never calls the setter still gets EluDiffusion's rows.
  *    Added without a bump (new symbols only, nothing of the above changes): adf_istft_config and the four adf_istft_* entry points;
- *    the four adf_stft_* entry points (WaveToSpec), which take the same adf_istft_config. */
+ *    the four adf_stft_* entry points (WaveToSpec), which take the same adf_istft_config; adf_debug_tap_stats and adf_debug_up_tile_plan. */
 #define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
@@ -231,6 +231,13 @@ int adf_sampler_nfe(const adf_sampler_desc* desc, const float* sigmas_host, int 
  * fp32 [B][C][L].  Names follow oracle/unet1d.py taps ("to_in", "down0.conv", "down0.block1", "mid.attn", ...). */
 int adf_debug_tap_shape(adf_handle* h, const char* name, int* C, int* L);
 int adf_debug_tap_copy(adf_handle* h, const char* name, float* out_fp32, void* stream);
+/* The GroupNorm statistics that the launch which stored tap `name` reduced with it: [B][groups][2] doubles (sum, sum of squares per sample and
+ * group) copied to out_host (host memory; may be null to ask only for *groups).  An error if that tensor was stored without statistics. */
+int adf_debug_tap_stats(adf_handle* h, const char* name, double* out_host, int* groups, void* stream);
+/* Host arithmetic only (no device is touched): the tile plan of the transposed-conv kernel (csrc/adf_gemm_up.h) for B samples of L input rows of
+ * one of its four shapes (cin -> cout, factor f): rows per tile, work items (sample x tile x column pass), rounds of 256 workgroups, and the
+ * rows of a sample's last tile past L.  Returns nonzero for any other shape. */
+int adf_debug_up_tile_plan(int cin, int cout, int f, int B, int L, int* tile_rows, int* items, int* rounds, int* dead_rows);
 /* The dynamic threshold alone, in place on x_dev [B][per_sample] (tests: exactness of the order statistics against torch.quantile). */
 int adf_debug_dyn_threshold(adf_handle* h, float* x_dev, int B, long long per_sample, float quantile, void* stream);
 /* The (c_in, c_noise, c_skip, c_out) rows of the last adf_sampler_run on this handle, one per denoiser evaluation in order: copies
