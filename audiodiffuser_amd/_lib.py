@@ -20,6 +20,7 @@ DTYPE_F32, DTYPE_BF16, DTYPE_F32X3 = 0, 1, 2
 FLAG_SEPARATE_GN_STATS = 1
 SAMPLER_EDM, SAMPLER_EDM_ALPHA, SAMPLER_DPM_MULTISTEP, SAMPLER_DPM2, SAMPLER_ADPM2 = 0, 1, 2, 3, 4
 SAMPLER_LMS, SAMPLER_DPM_SINGLESTEP, SAMPLER_DPM2M, SAMPLER_UNIPC, SAMPLER_ADPMPP2S = 5, 6, 7, 8, 9
+SAMPLER_RF_EULER = 10    # ADF_SAMPLER_RF_EULER (ReflowEulerSampler)
 
 
 class AdfNetConfig(C.Structure):
@@ -107,6 +108,7 @@ class AdfIstftConfig(C.Structure):
 
 FLAG_NEAREST_UPSAMPLE = 2  # ADF_FLAG_NEAREST_UPSAMPLE
 PRECOND_EDM, PRECOND_VE, PRECOND_VP, PRECOND_V_EDM = 0, 1, 2, 3      # ADF_PRECOND_* (adf_set_preconditioning)
+PRECOND_RF, PRECOND_RF_EDM = 4, 5                                    # ReFlow(for_edm=False) / ReFlow(for_edm=True)
 ABI_VERSION = 7          # ADF_ABI_VERSION of the header this binding was written against
 
 EXPORTS = {

@@ -236,6 +236,8 @@ int adf_set_preconditioning(adf_handle* h, int kind, double beta_min, double bet
         case ADF_PRECOND_EDM: pc.kind = ADF_PRECOND_KIND_EDM; break;
         case ADF_PRECOND_VE: pc.kind = ADF_PRECOND_KIND_VE; break;
         case ADF_PRECOND_V_EDM: pc.kind = ADF_PRECOND_KIND_V_EDM; break;
+        case ADF_PRECOND_RF: pc.kind = ADF_PRECOND_KIND_RF; break;
+        case ADF_PRECOND_RF_EDM: pc.kind = ADF_PRECOND_KIND_RF_EDM; break;
         case ADF_PRECOND_VP:
             if (!(beta_d != 0.0) || !std::isfinite(beta_min) || !std::isfinite(beta_d) || !std::isfinite(M))
                 return fail(h, "adf_set_preconditioning: ADF_PRECOND_VP needs finite beta_min, beta_d != 0 and M");
@@ -244,7 +246,7 @@ int adf_set_preconditioning(adf_handle* h, int kind, double beta_min, double bet
             pc.beta_min2 = (float)(beta_min * beta_min); pc.two_beta_d = (float)(2.0 * beta_d);
             pc.beta_min = (float)beta_min; pc.beta_d = (float)beta_d; pc.m_minus_1 = (float)(M - 1.0);
             break;
-        default: return fail(h, "adf_set_preconditioning: unknown kind (ADF_PRECOND_EDM, _VE, _VP, _V_EDM)");
+        default: return fail(h, "adf_set_preconditioning: unknown kind (ADF_PRECOND_EDM, _VE, _VP, _V_EDM, _RF, _RF_EDM)");
     }
     h->precond = pc;
     return 0;
@@ -283,7 +285,8 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
         if (!h->cond_on || h->cond_B != B) return fail(h, "class-conditional network: call adf_set_condition with the labels of this batch first");
         if (h->cond_scale != 1.0f && ensure_cfg_buffers(h, p)) return 1;
     }
-    if (h->unclipped() && !h->net->unclipped_epilogue && ensure_cfg_buffers(h, p)) return 1;     // unclipped estimate without a mode 2 epilogue: raw pass + combine (denoise_io)
+    // unclipped estimate without a mode 2 epilogue: raw pass + combine (denoise_io); the raw kind (ReFlow(for_edm=False)) combines only under guidance (above)
+    if (h->unclipped() && !h->raw_output() && !h->net->unclipped_epilogue && ensure_cfg_buffers(h, p)) return 1;
     if (h->dyn_q > 0.0f) {                               // buffers of the dynamic threshold: allocated before any capture starts
         if (ensure_cfg_buffers(h, p)) return 1;
         if (!p->dyn_scale) {

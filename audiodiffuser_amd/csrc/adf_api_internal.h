@@ -6,7 +6,7 @@
 //   adf_net_adm.hip        AdmNet: ADM UNetModel (unet2d_oai.py:382-635): adf_adm_create, registry, walk
 //   adf_net_unet2d.hip     Unet2dNet: Imagen-style UNet2dBase (unet2d.py:622-972), exact fp32: adf_unet2d_create, registry, walk
 //   adf_walk2d.h           what the two 2-D walks share: fine GroupNorm statistics, the conv launch, the conditioning prologue
-//   adf_sampler.hip        denoise wrappers; the ten sampler drivers (sampler_edm.py, stochastic_sampler_edm.py), written on SamplerCtx's
+//   adf_sampler.hip        denoise wrappers; the eleven sampler drivers (sampler_edm.py, stochastic_sampler_edm.py, sampler_rf.py), written on SamplerCtx's
 //                          members (below), which own the split between the counting pass and the real pass; count_sampler, sampler_draws
 //   adf_bench_replay.hip   adf_bench_* instrumentation
 // A handle owns one Net (below).  This header, adf_api.hip and adf_sampler.hip know a network only through that interface.
@@ -161,7 +161,9 @@ struct adf_handle {
     float cond_scale = 1.0f;
     Precond precond;                                     // which diffusion class's rows every evaluation uses (adf_set_preconditioning); sigma_data is filled per call
     Precond precond_for(float sigma_data) const { Precond pc = precond; pc.sigma_data = sigma_data; return pc; }
-    bool unclipped() const { return precond.kind == ADF_PRECOND_KIND_V_EDM; }      // VDiffusion(for_edm=True) returns v_to_x0 as it is (diffusion.py:326)
+    // VDiffusion(for_edm=True) returns v_to_x0 as it is (diffusion.py:326), and ReFlow never clips in either mode (:388-418)
+    bool unclipped() const { return precond.kind == ADF_PRECOND_KIND_V_EDM || precond.kind == ADF_PRECOND_KIND_RF || precond.kind == ADF_PRECOND_KIND_RF_EDM; }
+    bool raw_output() const { return precond.kind == ADF_PRECOND_KIND_RF; }         // ReFlow(for_edm=False): the row is (1, t, 0, 1), the estimate is the network output
     float dyn_q = 0.0f;                                  // > 0: dynamic thresholding at this quantile instead of clamp(-1, 1) (adf_set_dynamic_threshold)
     long long* cond_classes = nullptr;  // [cond_B]
     float* cond_emb = nullptr;          // [cond_B + 1][cdim], last row = null embedding

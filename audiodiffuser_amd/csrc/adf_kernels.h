@@ -46,7 +46,7 @@ const char* launch_to_out(const void* h, const float* w, float* out, int dtype, 
 
 // Which formulas turn a sigma into its row (adf_set_preconditioning); the constants are rounded to fp32 from the doubles the reference holds them in
 // (torch rounds a Python scalar operand to the tensor's dtype): beta_min2 = beta_min ** 2, two_beta_d = 2 * beta_d, m_minus_1 = M - 1.
-enum { ADF_PRECOND_KIND_EDM = 0, ADF_PRECOND_KIND_VE = 1, ADF_PRECOND_KIND_VP = 2, ADF_PRECOND_KIND_V_EDM = 3 };
+enum { ADF_PRECOND_KIND_EDM = 0, ADF_PRECOND_KIND_VE = 1, ADF_PRECOND_KIND_VP = 2, ADF_PRECOND_KIND_V_EDM = 3, ADF_PRECOND_KIND_RF = 4, ADF_PRECOND_KIND_RF_EDM = 5 };
 struct Precond {
     int kind = ADF_PRECOND_KIND_EDM;
     float sigma_data = 1.0f;                                                      // EDM
@@ -116,6 +116,10 @@ const char* launch_unipc(float* out, const float* x, const UniPcArgs& a, long lo
 const char* launch_dstep(float* x_next, const float* x_base, const float* x_eval, const float* den, float sigma, float dt, long long n,
                          hipStream_t st);
 const char* launch_clamp(float* x, long long n, hipStream_t st);
+// ReflowEulerSampler (sampler_rf.py:41, :50): the denoiser output v is the velocity itself.  x_next = x + dt * v
+const char* launch_rf_euler(float* x_next, const float* x, const float* v, float dt, long long n, hipStream_t st);
+// x_next = x + half_dt * (v + v2)
+const char* launch_rf_heun(float* x_next, const float* x, const float* v, const float* v2, float half_dt, long long n, hipStream_t st);
 
 const char* launch_nlc_to_ncl_f32(const void* x, float* y, int bf16, int B, int L, int C, hipStream_t st);
 

@@ -1291,7 +1291,8 @@ const char* launch_to_out(const void* h, const float* w, float* out, int dtype, 
 
 // =====================================================================================================
 // Preconditioning scalars: coef[b] = (c_in, c_noise, c_skip, c_out) of one sigma, fp32 in the reference's order of operations
-// (diffusion.py: EluDiffusion :232-241, VEDiffusion :107-116, VPDiffusion :156-170, VDiffusion(for_edm=True) :310-313 + v_to_x0 :290).
+// (diffusion.py: EluDiffusion :232-241, VEDiffusion :107-116, VPDiffusion :156-170, VDiffusion(for_edm=True) :310-313 + v_to_x0 :290,
+// ReFlow :379-418 in both modes).
 // Every operation of the new branches is rounded to fp32 on its own (through double and a cast, which the compiler cannot contract): torch rounds
 // sigma^2 before it adds 1, and at the low end of VPSchedule ln(1 + sigma^2) keeps three digits, so that rounding decides c_noise -- and with c_noise
 // in the hundreds one ulp of it is 1e-4 rad of the sinusoidal embedding's phase.  The EDM branch is compiled as it always was.
@@ -1329,6 +1330,18 @@ __device__ __forceinline__ void precond_row(const Precond& pc, float s, float* _
         row[1] = logsnr;
         row[2] = precond_mul(alphat, alphat);                             // v_to_x0 multiplies the scaled input by alphat again
         row[3] = -sigmat;
+    } else if (pc.kind == ADF_PRECOND_KIND_RF) {                        // ReFlow(for_edm=False) :388-418: the "sigma" is the time t, the result the raw velocity
+        row[0] = 1.0f;
+        row[1] = s;
+        row[2] = 0.0f;
+        row[3] = 1.0f;
+    } else if (pc.kind == ADF_PRECOND_KIND_RF_EDM) {                    // ReFlow(for_edm=True): t = sigma_to_t :379-380, x_in = x (1 - t) :402, x0 = x_in - v t :383
+        const float t = precond_div(s, precond_add(s, 1.0f));
+        const float one_minus_t = precond_add(1.0f, -t);
+        row[0] = one_minus_t;
+        row[1] = t;
+        row[2] = one_minus_t;
+        row[3] = -t;
     } else {
         const float sd = pc.sigma_data;
         const float s2 = s * s, d2 = sd * sd;
@@ -1742,6 +1755,46 @@ const char* launch_unipc(float* out, const float* x, const UniPcArgs& a, long lo
 const char* launch_clamp(float* x, long long n, hipStream_t st) {
     hipLaunchKernelGGL(clamp_kernel, dim3(ew_grid(n)), dim3(256), 0, st, x, n);
     return ADF_LAUNCH_CHECK("clamp");
+}
+
+// ReflowEulerSampler.step (sampler_rf.py:41, :50): the denoiser output is the velocity, so the updates read no sigma.  Each operation is rounded on
+// its own, as torch rounds the product before the sum (no fused multiply-add).  n4 = n / 4 float4 elements when every pointer is 16-byte aligned (the
+// sampler's state buffers are), else 0; the n - 4 n4 elements behind them go one by one.
+__device__ __forceinline__ float rf_euler_1(float x, float v, float dt) { return __fadd_rn(x, __fmul_rn(dt, v)); }
+__device__ __forceinline__ float rf_heun_1(float x, float v, float v2, float hdt) { return __fadd_rn(x, __fmul_rn(hdt, __fadd_rn(v, v2))); }
+__global__ void __launch_bounds__(256) rf_euler_kernel(float* __restrict__ xn, const float* __restrict__ x, const float* __restrict__ v, float dt,
+                                                       long long n4, long long n) {
+    const long long t0 = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+    for (long long i = t0; i < n4; i += stride) {
+        const float4 a = reinterpret_cast<const float4*>(x)[i], b = reinterpret_cast<const float4*>(v)[i];
+        reinterpret_cast<float4*>(xn)[i] = make_float4(rf_euler_1(a.x, b.x, dt), rf_euler_1(a.y, b.y, dt), rf_euler_1(a.z, b.z, dt), rf_euler_1(a.w, b.w, dt));
+    }
+    for (long long i = 4 * n4 + t0; i < n; i += stride) xn[i] = rf_euler_1(x[i], v[i], dt);
+}
+__global__ void __launch_bounds__(256) rf_heun_kernel(float* __restrict__ xn, const float* __restrict__ x, const float* __restrict__ v,
+                                                      const float* __restrict__ v2, float hdt, long long n4, long long n) {
+    const long long t0 = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+    for (long long i = t0; i < n4; i += stride) {
+        const float4 a = reinterpret_cast<const float4*>(x)[i], b = reinterpret_cast<const float4*>(v)[i], c = reinterpret_cast<const float4*>(v2)[i];
+        reinterpret_cast<float4*>(xn)[i] = make_float4(rf_heun_1(a.x, b.x, c.x, hdt), rf_heun_1(a.y, b.y, c.y, hdt), rf_heun_1(a.z, b.z, c.z, hdt),
+                                                       rf_heun_1(a.w, b.w, c.w, hdt));
+    }
+    for (long long i = 4 * n4 + t0; i < n; i += stride) xn[i] = rf_heun_1(x[i], v[i], v2[i], hdt);
+}
+static inline long long rf_vec4(long long n, const void* a, const void* b, const void* c, const void* d) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) ? 0 : n / 4;
+}
+const char* launch_rf_euler(float* x_next, const float* x, const float* v, float dt, long long n, hipStream_t st) {
+    if (n < 1 || x_next == x || x_next == v) return "rf_euler: bad arguments (the output must not alias an input)";
+    const long long n4 = rf_vec4(n, x_next, x, v, nullptr);
+    hipLaunchKernelGGL(rf_euler_kernel, dim3(ew_grid(n4 ? n4 : n)), dim3(256), 0, st, x_next, x, v, dt, n4, n);
+    return ADF_LAUNCH_CHECK("rf_euler");
+}
+const char* launch_rf_heun(float* x_next, const float* x, const float* v, const float* v2, float half_dt, long long n, hipStream_t st) {
+    if (n < 1 || x_next == x || x_next == v || x_next == v2) return "rf_heun: bad arguments (the output must not alias an input)";
+    const long long n4 = rf_vec4(n, x_next, x, v, v2);
+    hipLaunchKernelGGL(rf_heun_kernel, dim3(ew_grid(n4 ? n4 : n)), dim3(256), 0, st, x_next, x, v, v2, half_dt, n4, n);
+    return ADF_LAUNCH_CHECK("rf_heun");
 }
 
 // =====================================================================================================

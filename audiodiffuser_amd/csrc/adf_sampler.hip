@@ -38,12 +38,14 @@ int ensure_cfg_buffers(adf_handle* h, Plan* p) {
 // nets, and under guidance, it is the raw pass + cfg_combine without the clamp.
 int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s) {
     const bool cfg = h->cdim > 0 && h->cond_on && h->cond_scale != 1.0f;
-    const bool noclip = h->unclipped();              // VDiffusion(for_edm=True): no clamp, and dynamic_threshold is stored but never read (diffusion.py:326)
+    const bool noclip = h->unclipped();              // VDiffusion(for_edm=True), ReFlow: no clamp, and dynamic_threshold is never read (diffusion.py:326, :388-418)
+    const bool raw = h->raw_output();                // ReFlow(for_edm=False): the estimate is the network output, so without guidance there is nothing to combine
     const bool dyn = h->dyn_q > 0.0f && !noclip;
-    // one pass with the preconditioning in the last kernel's epilogue: clamped on every net, unclipped on UNet2dBase (u2d_conv_out_raw_kernel mode 2)
-    if (!cfg && !dyn && (!noclip || h->net->unclipped_epilogue)) {
+    // one pass with the preconditioning in the last kernel's epilogue: clamped on every net, unclipped on UNet2dBase (u2d_conv_out_raw_kernel mode 2);
+    // the raw kind is the mode 0 pass written straight into `out` on every net
+    if (!cfg && !dyn && (!noclip || raw || h->net->unclipped_epilogue)) {
         if (cond_rows(h, p->B, false, io)) return 1;
-        io.out = out; io.mode = noclip ? 2 : 1;
+        io.out = out; io.mode = raw ? 0 : (noclip ? 2 : 1);
         return forward(h, p, io, s);
     }
     const long long per_sample = (long long)h->net->dims.out_channels * p->L;
@@ -607,6 +609,31 @@ int run_unipc(SamplerCtx& c, float** result) {
     return c.finish(x, result);
 }
 
+// ReflowEulerSampler: sampler_rf.py:54-70 (num_steps steps over sigmas[i], sigmas[i + 1]: the schedule must hold num_steps + 1 entries -- with fewer
+// the reference raises IndexError; final clamp), :24-52 (step).  The denoiser returns the velocity (ADF_PRECOND_RF).  dt = sigma_next - sigma and
+// 0.5 * dt are fp32 scalars, as the reference forms them on 0-dim fp32 tensors (the halving is exact).
+int run_rf_euler(SamplerCtx& c, float** result) {
+    const adf_sampler_desc& d = *c.d;
+    const int N = d.num_steps;
+    if (N < 1 || c.nsig < N + 1) return c.reject("ReflowEulerSampler: the schedule must hold num_steps + 1 sigmas (the reference indexes sigmas[i + 1])");
+    float *X = c.buf(0), *XN = c.buf(1), *XE = c.buf(3), *V = c.buf(5), *V2 = c.buf(6);
+    if (c.start(X)) return 1;
+    for (int i = 0; i < N; ++i) {
+        const float sg = c.sig[i], sn = c.sig[i + 1];
+        const float dt = sn - sg;
+        if (c.den(X, sg, V)) return 1;
+        if (c.run(launch_rf_euler, XE, X, V, dt)) return 1;
+        if (sn != 0.f && d.use_heun) {
+            if (c.den(XE, sn, V2)) return 1;
+            if (c.run(launch_rf_heun, XN, X, V, V2, 0.5f * dt)) return 1;
+            std::swap(X, XN);
+        } else {
+            std::swap(X, XE);
+        }
+    }
+    return c.finish(X, result);
+}
+
 int run_sampler(SamplerCtx& c, float** result) {
     switch (c.d->kind) {
         case ADF_SAMPLER_DPM2: return run_dpm2(c, result);
@@ -619,7 +646,8 @@ int run_sampler(SamplerCtx& c, float** result) {
         case ADF_SAMPLER_DPM2M: return run_dpm2m(c, result);
         case ADF_SAMPLER_UNIPC: return run_unipc(c, result);
         case ADF_SAMPLER_ADPMPP2S: return run_adpmpp2s(c, result);
-        default: return c.reject("unknown sampler kind");
+        case ADF_SAMPLER_RF_EULER: return run_rf_euler(c, result);
+        default: return c.reject("unknown sampler kind (ADF_SAMPLER_EDM .. ADF_SAMPLER_ADPMPP2S, ADF_SAMPLER_RF_EULER)");
     }
 }
 

@@ -1,6 +1,6 @@
 """``model.diffusion`` plugins: preconditioning + denoise wrapper
 (reference: src/models/components/diffusion.py:15-63 ``Diffusion``, :99-133 ``VEDiffusion``, :136-218 ``VPDiffusion``,
-:220-258 ``EluDiffusion``, :260-365 ``VDiffusion``).
+:220-258 ``EluDiffusion``, :260-365 ``VDiffusion``, :367-442 ``ReFlow``).
 
 ``denoise_fn`` keeps the reference signature.  When ``net`` is one of this package's HIP nets and the call
 is the inference case the whole thing -- c_in scaling, sigma embedding, network,
@@ -298,3 +298,58 @@ class VDiffusion(Diffusion):
         weight = _extend(self.loss_weight(logsnr_t), x.ndim)
         losses = (weight * (eps_pred - noise) ** 2 * mask).reshape(x.shape[0], -1).sum(dim=1)
         return losses / float(x[0].numel())
+
+
+class ReFlow(Diffusion):
+    """Rectified flow (diffusion.py:367-442).  ``for_edm=False``: ``denoise_fn`` returns the network's velocity ``net(x, t)`` as it is -- the
+    "sigma" it is given is already the time t in [0, 1] -- which is what ``ReflowEulerSampler`` and ``DPM2MSampler(reflow=True)`` integrate.
+    ``for_edm=True`` wraps the velocity net as an x0 denoiser over sigma = t / (1 - t) (``RFEDMSchedule``) for the ``sampler_edm`` samplers:
+    ``t = sigma / (sigma + 1)``, ``x_in = x (1 - t)``, ``x0 = x_in - v t``.  Neither mode clips.  The reference multiplies the [B, C, ...] input by
+    the [B] vector ``1 - t`` as it is, which broadcasts against the LAST axis and so only runs for B = 1 (or B = W); the per-sample factors are
+    extended to [B, 1, ...] here, which gives what the reference gives sample by sample (as ``VDiffusion`` does)."""
+
+    _clips = False
+
+    def __init__(self, for_edm: bool = False):
+        super().__init__(0.0)
+        self.for_edm = for_edm
+
+    def _precond(self):
+        return (_lib.PRECOND_RF_EDM if self.for_edm else _lib.PRECOND_RF, 0.0, 1.0, 1.0)
+
+    # diffusion.py:379-386
+    def sigma_to_t(self, t):
+        return t / (t + 1)
+
+    def v_to_x0(self, x_noisy: Tensor, v_pred: Tensor, sigmas: Tensor) -> Tensor:
+        return x_noisy - v_pred * sigmas
+
+    def v_to_eps(self, x_noisy: Tensor, v_pred: Tensor, sigmas: Tensor) -> Tensor:
+        return x_noisy + v_pred * (1 - sigmas)
+
+    # diffusion.py:388-418.  On the device the two modes are the rows (c_in, c_noise, c_skip, c_out) = (1, t, 0, 1) and (1 - t, t, 1 - t, -t).
+    def _compat_denoise(self, x_noisy: Tensor, net, inference: bool, cond_scale: float, sigmas: Tensor, kwargs: dict) -> Tensor:
+        t = None
+        if self.for_edm:
+            sigmas = self.sigma_to_t(sigmas)
+            t = _extend(sigmas, x_noisy.ndim)
+            x_noisy = x_noisy * (1 - t)
+        if inference:
+            v_pred = net(x_noisy, sigmas, cond_drop_prob=0.0, **kwargs)
+            if cond_scale != 1.0:
+                null = net(x_noisy, sigmas, cond_drop_prob=1.0, **kwargs)
+                v_pred = null + (v_pred - null) * cond_scale
+        else:
+            v_pred = net(x_noisy, sigmas, **kwargs)
+        return self.v_to_x0(x_noisy, v_pred, t) if self.for_edm else v_pred
+
+    # diffusion.py:420-442 (training loss on the velocity; `sigmas` are times in [0, 1])
+    def forward(self, x: Tensor, net: nn.Module, sigmas: Tensor, inference: bool = False, cond_scale: float = 1.0, **kwargs) -> Tensor:
+        self._training_guard(net)
+        t = sigmas
+        t_padded = _extend(sigmas, x.ndim)
+        z1 = torch.randn_like(x)
+        zt = (1 - t_padded) * x + t_padded * z1
+        zt, t = zt.to(x.dtype), t.to(x.dtype)
+        vtheta = self.denoise_fn(zt, net, sigmas=t, inference=inference, cond_scale=cond_scale, **kwargs)
+        return ((z1 - x - vtheta) ** 2).mean(dim=list(range(1, x.ndim)))

@@ -1,6 +1,6 @@
-"""``model.sampler`` plugins: EDM-family sampling loops
+"""``model.sampler`` plugins: EDM-family sampling loops and the rectified-flow Euler / Heun loop
 (reference: src/models/components/sampler_edm.py:229-300 ``EDMAlphaSampler``, :302-397 ``EDMSampler``,
-:495-805 ``DPMSampler``).
+:495-805 ``DPMSampler``; src/models/components/sampler_rf.py:7-70 ``ReflowEulerSampler``).
 
 Constructor kwargs and ``forward(noise, fn, net, sigmas, **kwargs)`` follow the reference.  When ``fn``
 is the ``denoise_fn`` of one of this package's diffusion classes and ``net`` one of its HIP nets, the whole step
@@ -33,7 +33,7 @@ REQUIRE_NATIVE = os.environ.get("ADF_REQUIRE_NATIVE", "0") not in ("", "0")
 def _native_pair(fn: Callable, net, cond_scale: float, kwargs: dict, noise: Optional[Tensor] = None,
                  who: str = "sampler") -> Optional[Diffusion]:
     """The whole loop runs inside the HIP library when ``fn`` is the ``denoise_fn`` of one of this package's diffusion classes
-    (``EluDiffusion``, ``VEDiffusion``, ``VPDiffusion``, ``VDiffusion(for_edm=True)``), ``net`` one of its HIP nets and ``noise``
+    (``EluDiffusion``, ``VEDiffusion``, ``VPDiffusion``, ``VDiffusion(for_edm=True)``, ``ReFlow`` in both modes), ``net`` one of its HIP nets and ``noise``
     lives on a ROCm device.  The only conditioning it understands is ``classes`` (labels) on a
     class-conditional net, where ``cond_scale != 1`` is classifier-free guidance (two network passes per evaluation).
     Returns the owner of ``fn`` (-> device loop) or None (-> interface-compatibility branch)."""
@@ -96,7 +96,7 @@ def _prep(noise: Tensor) -> Tensor:
 
 
 class _Sampler(nn.Module):
-    """What the ten samplers share: the way into the device loop.  A sampler gives ``_desc`` (its fields of the descriptor), ``cond_scale``
+    """What the eleven samplers share: the way into the device loop.  A sampler gives ``_desc`` (its fields of the descriptor), ``cond_scale``
     and, if its reference loop draws noise, ``_draw_plan``."""
 
     def _draw_plan(self, sigmas: Tensor) -> Optional[Tuple[int, bool]]:
@@ -345,6 +345,39 @@ class DPM2MSampler(_Sampler):
                 h_d = (h_max + h_min) / 2
                 x = (t_min / t_max) * x - (-h_d).expm1() * ((1 + 1 / (2 * r)) * den - (1 / (2 * r)) * old)
             old = den
+        return x.clamp(-1.0, 1.0)
+
+
+class ReflowEulerSampler(_Sampler):
+    """Rectified-flow Euler sampler with a fixed schedule (sampler_rf.py:7-70): ``fn`` returns the velocity (``ReFlow(for_edm=False)``), one
+    evaluation per step plus a Heun correction wherever ``sigma_next != 0``; the result is clamped to [-1, 1].  The loop reads
+    ``sigmas[i + 1]`` for ``i < num_steps``: the schedule must hold ``num_steps + 1`` entries (``LinearSchedule(1, 0, num_steps + 1)``); with
+    ``num_steps`` entries the reference raises IndexError on its last step, and so does this class, before anything runs."""
+
+    def __init__(self, num_steps: int = 200, cond_scale: float = 1.0, use_heun: bool = True, use_graph: bool = True):
+        super().__init__()
+        self.num_steps, self.cond_scale, self.use_heun, self.use_graph = num_steps, cond_scale, use_heun, use_graph
+
+    def _desc(self, sigma_data: float) -> "_lib.AdfSamplerDesc":
+        return _lib.make_sampler_desc(_lib.SAMPLER_RF_EULER, self.num_steps, sigma_data, self.use_graph, use_heun=int(bool(self.use_heun)))
+
+    @torch.no_grad()
+    def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, **kwargs) -> Tensor:
+        if len(sigmas) < self.num_steps + 1:
+            raise IndexError(f"index {self.num_steps} is out of bounds for dimension 0 with size {len(sigmas)}")
+        y = self._native(noise, fn, net, sigmas, kwargs)
+        if y is not None:
+            return y
+        # ---- interface-compatibility branch (sampler_rf.py:24-70) ---------------------------------
+        x = sigmas[0] * noise
+        for i in range(self.num_steps):
+            s, s_next = sigmas[i], sigmas[i + 1]
+            v = fn(x, net=net, sigma=s, inference=True, cond_scale=self.cond_scale, **kwargs)
+            x_next = x + (s_next - s) * v
+            if s_next != 0 and self.use_heun:
+                v_next = fn(x_next, net=net, sigma=s_next, inference=True, cond_scale=self.cond_scale, **kwargs)
+                x_next = x + 0.5 * (s_next - s) * (v + v_next)
+            x = x_next
         return x.clamp(-1.0, 1.0)
 
 

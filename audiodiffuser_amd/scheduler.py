@@ -1,4 +1,4 @@
-"""``model.noise_scheduler`` plugins (reference: src/models/components/scheduler.py:6-103): the same torch ops in the same order,
+"""``model.noise_scheduler`` plugins (reference: src/models/components/scheduler.py:6-120): the same torch ops in the same order,
 so every schedule equals the reference's bit for bit.
 
 The Lightning module stores ``noise_scheduler()`` once (diffunet_complex_module.py:64), i.e. the
@@ -90,3 +90,18 @@ class VSchedule(nn.Module):
         alpha_t = torch.sqrt(torch.sigmoid(logsnr_t))
         sigma_t = torch.sqrt(torch.sigmoid(-logsnr_t))
         return sigma_t / alpha_t
+
+
+class RFEDMSchedule(nn.Module):
+    """scheduler.py:105-120: the rectified-flow time grid ``t = linspace(start, end, num_steps)`` as the EDM sigma ``t / (1 - t)`` that
+    ``ReFlow(for_edm=True)`` maps back (``t = sigma / (sigma + 1)``).  As in the reference the defaults give ``inf`` first (start = 1) and a last
+    sigma of 0, which the EDM-family samplers divide by: use ``start < 1`` and ``end > 0``."""
+
+    def __init__(self, start: float = 1.0, end: float = 0.0, num_steps: int = 50):
+        super().__init__()
+        assert start <= 1.0 and end >= 0.0, "start must be less than or equal to 1.0 and end must be greater than or equal to 0.0"
+        self.start, self.num_steps, self.end = start, num_steps, end
+
+    def forward(self) -> Tensor:
+        sigmas = torch.linspace(self.start, self.end, self.num_steps)
+        return sigmas / (1 - sigmas)

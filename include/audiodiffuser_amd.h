@@ -53,7 +53,9 @@ extern "C" {
  *    style of adf_set_dynamic_threshold: adf_sampler_desc and the argument list of adf_denoise are unchanged, so a caller that fills only the
  *    fields of version 6 and never calls the setter still gets EluDiffusion's rows.
  *    Added without a bump (new symbols only, nothing of the above changes): adf_istft_config and the four adf_istft_* entry points;
- *    the four adf_stft_* entry points (WaveToSpec), which take the same adf_istft_config; adf_debug_tap_stats and adf_debug_up_tile_plan. */
+ *    the four adf_stft_* entry points (WaveToSpec), which take the same adf_istft_config; adf_debug_tap_stats and adf_debug_up_tile_plan.
+ *    Also without a bump (new values of existing int arguments / fields; no struct grows and no argument list changes, and a library of version 7 without
+ *    them refuses both with its "unknown kind" errors): ADF_PRECOND_RF / ADF_PRECOND_RF_EDM (ReFlow) and ADF_SAMPLER_RF_EULER (ReflowEulerSampler). */
 #define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
@@ -96,12 +98,14 @@ typedef struct adf_net_config {
 #define ADF_SAMPLER_UNIPC 8     /* UniPCSampler (variant bh2), order 1..3, x0 or noise prediction, both spacings   sampler_edm.py:807-1053 */
 #define ADF_SAMPLER_DPM_SINGLESTEP 6 /* DPMSampler(multisteps=False, x0_pred=True) sampler_edm.py:568-622, :769-805 */
 #define ADF_SAMPLER_ADPMPP2S 9  /* ADPMPP2SSampler ("DPM++ 2S a Karras", ancestral; one draw per step with sigma_next > 0)   stochastic_sampler_edm.py:102-178 */
+#define ADF_SAMPLER_RF_EULER 10 /* ReflowEulerSampler (rectified flow: Euler, or Heun where sigma_next != 0); the denoiser output is the velocity (ADF_PRECOND_RF);
+                                   needs num_steps + 1 sigmas; reads only num_steps, use_heun, use_graph; final clamp   sampler_rf.py:7-70 */
 
 typedef struct adf_sampler_desc {
     int32_t kind;
     int32_t num_steps;   /* the reference constructor's num_steps */
     float s_tmin, s_tmax, s_churn, s_noise;  /* EDM */
-    int32_t use_heun;    /* EDM, EDM_ALPHA */
+    int32_t use_heun;    /* EDM, EDM_ALPHA, RF_EULER */
     float alpha;         /* EDM_ALPHA */
     int32_t order;       /* DPM, UniPC: 1..3; LMS: 1..4 */
     float sigma_data;    /* EluDiffusion.sigma_data */
@@ -181,12 +185,19 @@ int adf_set_dynamic_threshold(adf_handle* h, float quantile);
  *   ADF_PRECOND_VP     VPDiffusion   :156-170  ((s^2 + 1)^-1/2, (M - 1) t(s), 1, -s), t(s) = (sqrt(beta_min^2 + 2 beta_d ln(1 + s^2)) - beta_min) / beta_d
  *   ADF_PRECOND_V_EDM  VDiffusion(for_edm=True) :296-326  (a, -2 ln s, a^2, -sqrt(sigmoid(2 ln s))), a = sqrt(sigmoid(-2 ln s)).  The estimate is returned
  *                                              UNCLIPPED, as in the reference: neither the clamp nor the dynamic threshold applies.
+ *   ADF_PRECOND_RF     ReFlow(for_edm=False)    :388-418  (1, s, 0, 1): the "sigma" is the rectified-flow time t in [0, 1] and the result is the network's
+ *                                              velocity itself (under guidance: the guided velocity), UNCLIPPED.  What ADF_SAMPLER_RF_EULER and
+ *                                              ADF_SAMPLER_DPM2M with `reflow` drive.
+ *   ADF_PRECOND_RF_EDM ReFlow(for_edm=True)     :379-418  (1 - t, t, 1 - t, -t), t = s / (s + 1): x0 = (1 - t) x - t v, UNCLIPPED, for the EDM-family samplers
+ *                                              on RFEDMSchedule (sigma = t / (1 - t)).
  * beta_min, beta_d, M are read for ADF_PRECOND_VP only (doubles: beta_min^2, 2 beta_d and M - 1 are formed in double and then rounded to fp32, as torch
  * rounds the reference's Python scalars); sigma_data is ignored by every kind but ADF_PRECOND_EDM. */
 #define ADF_PRECOND_EDM 0
 #define ADF_PRECOND_VE 1
 #define ADF_PRECOND_VP 2
 #define ADF_PRECOND_V_EDM 3
+#define ADF_PRECOND_RF 4
+#define ADF_PRECOND_RF_EDM 5
 int adf_set_preconditioning(adf_handle* h, int kind, double beta_min, double beta_d, double M);
 /* A WaveNetNoise handle.  x / out of adf_net_forward, adf_denoise, adf_sampler_run are [B][1][T] (the reference's forward takes
  * audio [B][T] and returns [B][1][T]: same memory); any T >= 1.  Debug taps: "y<n>" = input of residual layer n including its
