@@ -109,6 +109,8 @@ class AdfIstftConfig(C.Structure):
 FLAG_NEAREST_UPSAMPLE = 2  # ADF_FLAG_NEAREST_UPSAMPLE
 PRECOND_EDM, PRECOND_VE, PRECOND_VP, PRECOND_V_EDM = 0, 1, 2, 3      # ADF_PRECOND_* (adf_set_preconditioning)
 PRECOND_RF, PRECOND_RF_EDM = 4, 5                                    # ReFlow(for_edm=False) / ReFlow(for_edm=True)
+LOSS_X0_EDM, LOSS_X0_INV_SIGMA2, LOSS_RF = 0, 1, 2                    # ADF_LOSS_* (adf_diffusion_loss)
+LOSS_CHUNK = 4096        # kLossChunk of csrc/adf_loss.h: elements of a sample row per block of the loss kernels (tests build their row sweep around it)
 ABI_VERSION = 7          # ADF_ABI_VERSION of the header this binding was written against
 
 EXPORTS = {
@@ -135,6 +137,9 @@ EXPORTS = {
     "adf_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "adf_sampler_run": (C.c_int, [C.c_void_p, C.POINTER(AdfSamplerDesc), C.POINTER(C.c_float), C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "adf_diffusion_loss": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_int, C.c_int, C.c_void_p]),
+    "adf_loss_calls": (C.c_int64, [C.c_void_p]),
     "adf_sampler_nfe": (C.c_int, [C.POINTER(AdfSamplerDesc), C.POINTER(C.c_float), C.c_int]),
     "adf_debug_tap_shape": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "adf_debug_tap_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]),
@@ -152,6 +157,8 @@ EXPORTS = {
                                   C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p]),
     "adf_bench_wavenet_layer": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_double),
                                           C.POINTER(C.c_double), C.c_void_p]),
+    "adf_bench_loss_kernels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
     "adf_istft_create": (C.c_int, [C.POINTER(AdfIstftConfig), C.c_void_p, C.POINTER(C.c_void_p)]),
     "adf_istft_basis": (C.c_int, [C.POINTER(AdfIstftConfig), C.c_void_p, C.c_void_p, C.c_void_p]),
     "adf_istft_run": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),

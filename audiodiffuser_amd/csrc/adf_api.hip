@@ -260,12 +260,57 @@ int adf_denoise(adf_handle* h, const float* x_noisy, const float* sigmas_dev, fl
     if (get_plan(h, B, L, s, &p)) return 1;
     ++h->ctr.denoise_calls;
     if (!sigmas_dev) return denoise_scalar(h, p, x_noisy, sigma, sigma_data, out, s);
-    if (const char* e = launch_edm_coef(sigmas_dev, 0.f, B, h->precond_for(sigma_data), p->coef, s)) return fail(h, e);
-    FwdIO io;
-    io.x = x_noisy; io.t = p->coef + 1; io.t_stride = 4; io.nb = B;
-    io.coef = p->coef; io.coef_bstride = 4; io.x_noisy = x_noisy;
-    return denoise_io(h, p, io, out, s);
+    return denoise_rows(h, p, x_noisy, sigmas_dev, sigma_data, out, s);
 }
+
+// Diffusion.forward / ReFlow.forward under no_grad (diffusion.py:65-97, :185-218, :420-442): mix, one denoiser evaluation, weighted squared error
+// (adf_loss.h).  x_noisy and pred live in the first two sampler state buffers of the plan when the caller does not ask for them: a sampler run
+// starts from its own noise, so nothing of theirs is carried between calls.
+int adf_diffusion_loss(adf_handle* h, int kind, const float* x, const float* noise, const float* sigmas_dev, float sigma_data, float* losses,
+                       float* x_noisy_out, float* pred_out, int B, int L, void* stream) {
+    if (!h) return 1;
+    ADF_ON_DEVICE(h);
+    // adf_run_counters is left as it is, whatever the call enqueues (the network passes of the evaluation, a new plan's warm-up pass): adf_loss_calls is the loss's counter
+    struct KeepCounters { adf_handle* h; adf_run_counters c; ~KeepCounters() { h->ctr = c; } } keep_counters{h, h->ctr};
+    hipStream_t s = (hipStream_t)stream;
+    if (kind != ADF_LOSS_X0_EDM && kind != ADF_LOSS_X0_INV_SIGMA2 && kind != ADF_LOSS_RF)
+        return fail(h, "adf_diffusion_loss: unknown kind (ADF_LOSS_X0_EDM, _X0_INV_SIGMA2, _RF)");
+    if (!x) return fail(h, "adf_diffusion_loss: x is null");
+    if (!noise) return fail(h, "adf_diffusion_loss: noise is null");
+    if (!sigmas_dev) return fail(h, "adf_diffusion_loss: sigmas_dev is null");
+    if (!losses) return fail(h, "adf_diffusion_loss: losses is null");
+    if (kind == ADF_LOSS_X0_EDM && !(sigma_data > 0.0f)) return fail(h, "adf_diffusion_loss: sigma_data must be positive for ADF_LOSS_X0_EDM");
+    const NetDims& nd = h->net->dims;
+    if (nd.in_channels != nd.out_channels) return fail(h, "adf_diffusion_loss: the loss needs in_channels == out_channels");
+    if (B < 1 || L < 1) return fail(h, "adf_diffusion_loss: B and L must be positive");
+    {   // the outputs must not overlap an input or each other: every kernel of the call reads x (and noise) after x_noisy and pred are written
+        const size_t bytes = (size_t)B * nd.out_channels * L * sizeof(float);
+        auto overlap = [bytes](const float* a, const float* b) {
+            return a && b && (uintptr_t)a < (uintptr_t)b + bytes && (uintptr_t)b < (uintptr_t)a + bytes;
+        };
+        if (overlap(x_noisy_out, x) || overlap(x_noisy_out, noise)) return fail(h, "adf_diffusion_loss: x_noisy_out overlaps x or noise");
+        if (overlap(pred_out, x) || overlap(pred_out, noise)) return fail(h, "adf_diffusion_loss: pred_out overlaps x or noise");
+        if (overlap(pred_out, x_noisy_out)) return fail(h, "adf_diffusion_loss: pred_out overlaps x_noisy_out");
+    }
+    Plan* p;
+    if (get_plan(h, B, L, s, &p)) return 1;
+    const long long N = (long long)nd.out_channels * L;
+    if (!p->loss_partial) {
+        p->loss_partial = (double*)dalloc(h, (size_t)B * loss_chunks(N) * sizeof(double), p);
+        if (!p->loss_partial) return fail(h, "adf_diffusion_loss: device allocation failed for the block sums");
+    }
+    float* xn = x_noisy_out ? x_noisy_out : p->sb[0];
+    float* pred = pred_out ? pred_out : p->sb[1];
+    const int rf = kind == ADF_LOSS_RF;
+    if (const char* e = launch_loss_mix(xn, x, noise, sigmas_dev, rf, B, N, s)) return fail(h, e);
+    if (denoise_rows(h, p, xn, sigmas_dev, sigma_data, pred, s)) return 1;
+    if (const char* e = launch_loss_partial(p->loss_partial, pred, x, rf ? noise : nullptr, B, N, s)) return fail(h, e);
+    if (const char* e = launch_loss_finalize(losses, p->loss_partial, sigmas_dev, kind, sigma_data, B, N, s)) return fail(h, e);
+    ++h->loss_calls;
+    return 0;
+}
+
+int64_t adf_loss_calls(const adf_handle* h) { return h ? h->loss_calls : 0; }
 
 int adf_sampler_nfe(const adf_sampler_desc* desc, const float* sigmas_host, int n_sigmas) {
     return count_sampler(desc, sigmas_host, n_sigmas);

@@ -20,6 +20,7 @@
 #include "adf_transformer.h"
 #include "adf_resblock_small.h"
 #include "adf_resblock_split.h"
+#include "adf_loss.h"
 
 #include <algorithm>
 #include <cmath>
@@ -79,6 +80,7 @@ struct Plan {
     float* noise_stage = nullptr; float* out_stage = nullptr; float* inj_stage = nullptr; size_t inj_cap = 0;
     float* cfg_c = nullptr; float* cfg_n = nullptr;      // raw network outputs of the two CFG branches
     float* dyn_scale = nullptr;                          // [B] per-sample scales of the dynamic threshold
+    double* loss_partial = nullptr;                      // [B][loss_chunks(C * L)] block sums of adf_diffusion_loss, allocated by the first loss call on this plan
     // captured sampler loops, most recently used first; at most kMaxGraphsPerPlan are kept (the oldest is destroyed)
     std::vector<std::pair<std::string, hipGraphExec_t>> graphs;
     std::vector<void*> allocs;                            // device memory owned by this plan (released when the plan is evicted)
@@ -178,6 +180,7 @@ struct adf_handle {
     hipStream_t gstream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
     adf_run_counters ctr{};             // what the device loop has done so far (adf_get_counters): lets a test tell it from a host-side loop
+    int64_t loss_calls = 0;             // successful adf_diffusion_loss calls (adf_loss_calls; adf_run_counters must not grow at ABI version 7)
 };
 
 namespace adf_api {
@@ -330,6 +333,8 @@ int cond_rows(adf_handle* h, int B, bool null_branch, FwdIO& io);
 int ensure_cfg_buffers(adf_handle* h, Plan* p);
 int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s);
 int denoise_scalar(adf_handle* h, Plan* p, const float* x, float sigma, float sigma_data, float* out, hipStream_t s);
+// one evaluation with a sigma per sample (sigmas_dev [B] on the device): what adf_denoise enqueues, and the middle of adf_diffusion_loss
+int denoise_rows(adf_handle* h, Plan* p, const float* x, const float* sigmas_dev, float sigma_data, float* out, hipStream_t s);
 
 // One run of a sampler driver (adf_sampler.hip).  Every driver runs twice: a host-only counting pass (count_sampler: h == p == nullptr,
 // serves adf_sampler_nfe and the per-run sigma table) and the real pass, which enqueues the launches.  The members below own that split:

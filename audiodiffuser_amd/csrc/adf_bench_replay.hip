@@ -144,5 +144,48 @@ int adf_bench_wavenet_layer(adf_handle* h, int B, int T, int layer, int iters, f
     return 0;
 }
 
+int adf_bench_loss_kernels(adf_handle* h, int rf, int B, long long N, int iters, float* ms_mix, float* ms_partial, double* bytes_mix,
+                           double* bytes_partial, void* stream) {
+    if (!h) return 1;
+    ADF_ON_DEVICE(h);
+    if (!ms_mix || !ms_partial || !bytes_mix || !bytes_partial) return fail(h, "adf_bench_loss_kernels: null output");
+    if (B < 1 || B > 65535 || N < 1 || N > (1ll << 31) || iters < 1) return fail(h, "adf_bench_loss_kernels: bad B, N or iters");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = (size_t)B * (size_t)N;
+    float* buf[4] = {nullptr, nullptr, nullptr, nullptr};          // x, noise, x_noisy, pred: zero-filled, the kernels' time does not depend on the values
+    float* coef = nullptr; double* partial = nullptr;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    const char* err = nullptr;
+    for (int i = 0; i < 4 && !err; ++i)
+        if (hipMalloc(&buf[i], n * 4) != hipSuccess || hipMemsetAsync(buf[i], 0, n * 4, s) != hipSuccess) err = "adf_bench_loss_kernels: device allocation failed";
+    if (!err && (hipMalloc(&coef, (size_t)B * 4) != hipSuccess || hipMemsetAsync(coef, 0, (size_t)B * 4, s) != hipSuccess ||
+                 hipMalloc(&partial, (size_t)B * loss_chunks(N) * 8) != hipSuccess))
+        err = "adf_bench_loss_kernels: device allocation failed";
+    for (int i = 0; i < 3 && !err; ++i)
+        if (hipEventCreate(&ev[i]) != hipSuccess) err = "hipEventCreate failed";
+    for (int i = 0; i < 2 && !err; ++i) {
+        err = launch_loss_mix(buf[2], buf[0], buf[1], coef, rf, B, N, s);
+        if (!err) err = launch_loss_partial(partial, buf[3], buf[0], rf ? buf[1] : nullptr, B, N, s);
+    }
+    if (!err && hipEventRecord(ev[0], s) != hipSuccess) err = "hipEventRecord failed";
+    for (int i = 0; i < iters && !err; ++i) err = launch_loss_mix(buf[2], buf[0], buf[1], coef, rf, B, N, s);
+    if (!err && hipEventRecord(ev[1], s) != hipSuccess) err = "hipEventRecord failed";
+    for (int i = 0; i < iters && !err; ++i) err = launch_loss_partial(partial, buf[3], buf[0], rf ? buf[1] : nullptr, B, N, s);
+    if (!err && (hipEventRecord(ev[2], s) != hipSuccess || hipEventSynchronize(ev[2]) != hipSuccess)) err = "event sync failed";
+    float t_mix = 0.f, t_partial = 0.f;
+    if (!err && (hipEventElapsedTime(&t_mix, ev[0], ev[1]) != hipSuccess || hipEventElapsedTime(&t_partial, ev[1], ev[2]) != hipSuccess))
+        err = "hipEventElapsedTime failed";
+    if (err) (void)hipStreamSynchronize(s);                         // nothing of the buffers may still be in flight when they go
+    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    for (float* b : buf) if (b) (void)hipFree(b);
+    if (coef) (void)hipFree(coef);
+    if (partial) (void)hipFree(partial);
+    if (err) return fail(h, err);
+    *ms_mix = t_mix / (float)iters; *ms_partial = t_partial / (float)iters;
+    *bytes_mix = 12.0 * (double)n;                                  // two reads and one write of fp32
+    *bytes_partial = (rf ? 12.0 : 8.0) * (double)n;                 // pred and x, and the noise for the velocity loss
+    return 0;
+}
+
 
 }  // extern "C"

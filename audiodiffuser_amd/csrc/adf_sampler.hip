@@ -78,6 +78,14 @@ int denoise_scalar(adf_handle* h, Plan* p, const float* x, float sigma, float si
     return denoise_io(h, p, io, out, s);
 }
 
+int denoise_rows(adf_handle* h, Plan* p, const float* x, const float* sigmas_dev, float sigma_data, float* out, hipStream_t s) {
+    if (const char* e = launch_edm_coef(sigmas_dev, 0.f, p->B, h->precond_for(sigma_data), p->coef, s)) return fail(h, e);
+    FwdIO io;
+    io.x = x; io.t = p->coef + 1; io.t_stride = 4; io.nb = p->B;
+    io.coef = p->coef; io.coef_bstride = 4; io.x_noisy = x;
+    return denoise_io(h, p, io, out, s);
+}
+
 // ---- sampler drivers -----------------------------------------------------------------------------------
 // Each returns the buffer holding the final sample through *result.  Written on SamplerCtx's members (adf_api_internal.h), so the same
 // code is the counting pass and the real pass.

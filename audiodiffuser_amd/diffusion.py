@@ -10,6 +10,11 @@ clipping -- is one ``adf_denoise`` call; which class's formulas the device uses 
 For any other ``net`` (e.g. an unpickled reference module, diffunet_complex_module.py:239-242) the
 same arithmetic is expressed with tensor ops around ``net(...)``; that branch exists for interface
 compatibility and is not the accelerated path.
+
+``forward`` is the loss (``DiffUnetComplexModule.forward`` / ``validation_step``, diffunet_complex_module.py:104-125, :186-195).  Under
+``torch.no_grad()`` on a HIP net it is one ``adf_diffusion_loss`` call -- noising, the same ``adf_denoise`` evaluation, weighted per-sample squared
+error -- for the classes whose loss has an x0 or velocity form (``_loss_kind``); ``loss_route_refusal`` says for which calls, and every other
+call runs ``_tensor_loss``, the tensor ops this module has always used.
 """
 from __future__ import annotations
 
@@ -42,6 +47,34 @@ def conditioning_refusal(net: HipNet, cond_scale: float, kwargs: dict) -> Option
     return "conditioning keywords / cond_scale != 1 on an unconditional net" if extra or cond_scale != 1.0 else None
 
 
+def loss_route_refusal(diff: "Diffusion", net, x_is_cuda: bool, inference: bool, cond_scale: float, kwargs: dict) -> Optional[str]:
+    """None when ``diff.forward(x, net, sigmas, inference, cond_scale, **kwargs)`` is one ``adf_diffusion_loss`` call, otherwise why it stays on
+    the tensor route (``_tensor_loss``).  Host logic only: no device is touched."""
+    if diff._loss_kind() is None:
+        return f"{type(diff).__name__}'s loss has no device form (neither x0 nor velocity)"
+    if diff._precond() is None:
+        return "the device has no row form for this preconditioning"
+    if not isinstance(net, HipNet):
+        return "`net` is not one of this package's HIP nets"
+    if not x_is_cuda:
+        return "`x` is not on a ROCm device"
+    if not 0.0 <= diff.dynamic_threshold <= 1.0:
+        return "dynamic_threshold outside [0, 1]"
+    if "x_mask" in kwargs:
+        return "`x_mask` weights the loss per element"
+    if inference:
+        return conditioning_refusal(net, cond_scale, kwargs)
+    # not inferring, the reference calls net(x, c_noise, **kwargs): `cond_scale` is ignored and the label mask follows the net's cond_drop_prob
+    extra = {k for k, v in kwargs.items() if v is not None}
+    if not net.cfg.class_cond:
+        return "conditioning keywords on an unconditional net" if extra else None
+    if extra != {"classes"}:
+        return "a class-conditional net takes exactly the `classes` keyword"
+    if net.cond_drop_prob not in (0, 0.0, 1, 1.0):
+        return "cond_drop_prob other than 0 or 1 draws a random label mask"
+    return None
+
+
 class Diffusion(nn.Module):
     """What the preconditioned diffusion classes share (diffusion.py:15-97): ``denoise_fn`` with the native fast path and the
     tensor-op compatibility branch, and the training ``forward``.  Subclasses give ``get_scale_weights`` / ``loss_weight`` and the
@@ -58,6 +91,10 @@ class Diffusion(nn.Module):
     def _precond(self) -> Optional[tuple]:
         """(ADF_PRECOND_* kind, beta_min, beta_d, M) of ``adf_set_preconditioning``, or None when the device has no row form for it."""
         raise NotImplementedError
+
+    def _loss_kind(self) -> Optional[int]:
+        """The ADF_LOSS_* kind of ``adf_diffusion_loss`` this class's ``forward`` is, or None when the device has no form for it."""
+        return None
 
     def _not_native_note(self) -> str:
         return ""
@@ -119,9 +156,34 @@ class Diffusion(nn.Module):
             raise NotImplementedError(f"{type(self).__name__}.forward is the training loss; the HIP nets are an inference path without "
                                       "backward -- train the reference module and load its state_dict here, or call under torch.no_grad()")
 
-    # diffusion.py:65-98 (training loss; stock tensor ops, outside the accelerated path)
+    # diffusion.py:65-98
     def forward(self, x: Tensor, net: nn.Module, sigmas: Tensor, inference: bool = False, cond_scale: float = 1.0,
                 **kwargs) -> Tensor:
+        if loss_route_refusal(self, net, x.is_cuda, inference, cond_scale, kwargs) is None:
+            self._training_guard(net)
+            return self._device_loss(x, net, sigmas, inference, cond_scale, kwargs)
+        return self._tensor_loss(x, net, sigmas, inference=inference, cond_scale=cond_scale, **kwargs)
+
+    def _device_loss(self, x: Tensor, net: HipNet, sigmas: Tensor, inference: bool, cond_scale: float, kwargs: dict) -> Tensor:
+        """One ``adf_diffusion_loss`` call.  The noise is drawn first, once, on ``x``'s device, as ``_tensor_loss`` draws it: with the same seed both
+        routes see the same noise and leave the global generator in the same state."""
+        noise = torch.randn_like(x)
+        hd = net.native(x.device)
+        self._configure(hd)
+        if net.cfg.class_cond:
+            if inference:           # labels + two-pass guidance (diffusion.py:49-54)
+                hd.set_condition(kwargs["classes"], x.device, null_labels=False, cond_scale=float(cond_scale))
+            else:                   # net(x, c_noise, classes=...): the net's own cond_drop_prob, no guidance (:56)
+                hd.set_condition(kwargs["classes"], x.device, null_labels=bool(net.cond_drop_prob), cond_scale=1.0)
+        xf = x.detach().to(torch.float32).contiguous()
+        nf = noise.to(torch.float32).contiguous()
+        sv = sigmas.detach().to(device=x.device, dtype=torch.float32).reshape(-1).contiguous()
+        with torch.cuda.device(x.device):
+            return hd.diffusion_loss(self._loss_kind(), xf, nf, sv, self.sigma_data).to(x.dtype)
+
+    # diffusion.py:65-98 as stock tensor ops: the route of every call `loss_route_refusal` names a reason for
+    def _tensor_loss(self, x: Tensor, net: nn.Module, sigmas: Tensor, inference: bool = False, cond_scale: float = 1.0,
+                     **kwargs) -> Tensor:
         self._training_guard(net)
         noise = torch.randn_like(x)
         x_noisy = x + _extend(sigmas, x.ndim) * noise
@@ -144,6 +206,9 @@ class EluDiffusion(Diffusion):
 
     def _precond(self):
         return (_lib.PRECOND_EDM, 0.0, 1.0, 1.0)
+
+    def _loss_kind(self):
+        return _lib.LOSS_X0_EDM
 
     # diffusion.py:232-241
     def get_scale_weights(self, sigmas: Tensor, ex_dim: int) -> Tuple[Tensor, ...]:
@@ -169,6 +234,9 @@ class VEDiffusion(Diffusion):
     def _precond(self):
         return (_lib.PRECOND_VE, 0.0, 1.0, 1.0)
 
+    def _loss_kind(self):
+        return _lib.LOSS_X0_INV_SIGMA2
+
     # diffusion.py:107-116
     def get_scale_weights(self, sigmas: Tensor, ex_dim: int) -> Tuple:
         c_noise = (0.5 * sigmas).log()
@@ -192,6 +260,9 @@ class VPDiffusion(Diffusion):
     def _precond(self):
         return (_lib.PRECOND_VP, float(self.beta_min), float(self.beta_d), float(self.M))
 
+    def _loss_kind(self):
+        return _lib.LOSS_X0_INV_SIGMA2
+
     # diffusion.py:152-154
     def loss_weight(self, sigmas: Tensor) -> Tensor:
         return 1 / sigmas ** 2
@@ -211,7 +282,7 @@ class VPDiffusion(Diffusion):
         c_in = 1 / (sigmas ** 2 + 1).sqrt()
         return 1, -sigmas, c_in, c_noise
 
-    # diffusion.py:185-218: `sigmas` are times t, mapped to sigma first
+    # diffusion.py:185-218: `sigmas` are times t, mapped to sigma first (in torch, on either route: `_device_loss` and `_tensor_loss` take sigmas)
     def forward(self, x: Tensor, net: nn.Module, sigmas: Tensor, inference: bool = False, cond_scale: float = 1.0, **kwargs) -> Tensor:
         return super().forward(x, net, self.t_to_sigma(sigmas), inference=inference, cond_scale=cond_scale, **kwargs)
 
@@ -281,8 +352,8 @@ class VDiffusion(Diffusion):
             v_pred = net(x_noisy, sigmas, **kwargs)
         return self.v_to_x0(x_noisy, v_pred, alphat, sigmat) if self.for_edm else v_pred
 
-    # diffusion.py:328-365 (training loss on the noise prediction; `sigmas` are times in [0, 1])
-    def forward(self, x: Tensor, net: nn.Module, sigmas: Tensor, inference: bool = False, cond_scale: float = 1.0, **kwargs) -> Tensor:
+    # diffusion.py:328-365 (training loss on the noise prediction; `sigmas` are times in [0, 1]); no device form (`_loss_kind` is None)
+    def _tensor_loss(self, x: Tensor, net: nn.Module, sigmas: Tensor, inference: bool = False, cond_scale: float = 1.0, **kwargs) -> Tensor:
         self._training_guard(net)
         logsnr_t = self.shifted_cosine_transform(sigmas)
         alpha_t = _extend(torch.sqrt(torch.sigmoid(logsnr_t)), x.ndim)
@@ -317,6 +388,9 @@ class ReFlow(Diffusion):
     def _precond(self):
         return (_lib.PRECOND_RF_EDM if self.for_edm else _lib.PRECOND_RF, 0.0, 1.0, 1.0)
 
+    def _loss_kind(self):
+        return None if self.for_edm else _lib.LOSS_RF       # for_edm trains the same velocity through the x0 wrapper: tensor route
+
     # diffusion.py:379-386
     def sigma_to_t(self, t):
         return t / (t + 1)
@@ -344,7 +418,7 @@ class ReFlow(Diffusion):
         return self.v_to_x0(x_noisy, v_pred, t) if self.for_edm else v_pred
 
     # diffusion.py:420-442 (training loss on the velocity; `sigmas` are times in [0, 1])
-    def forward(self, x: Tensor, net: nn.Module, sigmas: Tensor, inference: bool = False, cond_scale: float = 1.0, **kwargs) -> Tensor:
+    def _tensor_loss(self, x: Tensor, net: nn.Module, sigmas: Tensor, inference: bool = False, cond_scale: float = 1.0, **kwargs) -> Tensor:
         self._training_guard(net)
         t = sigmas
         t_padded = _extend(sigmas, x.ndim)

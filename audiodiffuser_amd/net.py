@@ -155,6 +155,27 @@ class NativeHandle:
                                         C.c_void_p(_stream_ptr(x.device))), "adf_denoise")
         return out
 
+    def diffusion_loss(self, kind: int, x: torch.Tensor, noise: torch.Tensor, sigmas: torch.Tensor, sigma_data: float, keep: bool = False):
+        """``adf_diffusion_loss``: noising, one denoiser evaluation under the handle's state, weighted per-sample squared error.  ``x`` / ``noise``
+        fp32 contiguous [B, C, ...] on the handle's device, ``sigmas`` fp32 [B] there (times for ``LOSS_RF``).  Returns the [B] losses, with
+        ``keep`` also the noisy input and the denoiser output of the call."""
+        if noise.shape != x.shape or noise.device != x.device or sigmas.device != x.device or sigmas.numel() != x.shape[0]:
+            raise ValueError("noise must have the shape and device of x, sigmas one entry per batch element on that device")
+        for name, t in (("x", x), ("noise", noise), ("sigmas", sigmas)):
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous fp32 tensor")
+        losses = torch.empty((x.shape[0],), device=x.device, dtype=torch.float32)
+        x_noisy = torch.empty_like(x) if keep else None
+        pred = torch.empty_like(x) if keep else None
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        self.check(self.lib.adf_diffusion_loss(self.h, int(kind), ptr(x), ptr(noise), ptr(sigmas), float(sigma_data), ptr(losses), ptr(x_noisy),
+                                               ptr(pred), x.shape[0], self._length(x), C.c_void_p(_stream_ptr(x.device))), "adf_diffusion_loss")
+        return (losses, x_noisy, pred) if keep else losses
+
+    def loss_calls(self) -> int:
+        """Successful ``adf_diffusion_loss`` calls on this handle: how a caller, and every GPU loss test, tells that the device path ran."""
+        return int(self.lib.adf_loss_calls(self.h))
+
     def sampler_run(self, desc: "_lib.AdfSamplerDesc", sigmas_host: torch.Tensor, noise: torch.Tensor,
                     injected: Optional[torch.Tensor]) -> torch.Tensor:
         out = torch.empty_like(noise)

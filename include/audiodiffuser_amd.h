@@ -55,7 +55,9 @@ extern "C" {
  *    Added without a bump (new symbols only, nothing of the above changes): adf_istft_config and the four adf_istft_* entry points;
  *    the four adf_stft_* entry points (WaveToSpec), which take the same adf_istft_config; adf_debug_tap_stats and adf_debug_up_tile_plan.
  *    Also without a bump (new values of existing int arguments / fields; no struct grows and no argument list changes, and a library of version 7 without
- *    them refuses both with its "unknown kind" errors): ADF_PRECOND_RF / ADF_PRECOND_RF_EDM (ReFlow) and ADF_SAMPLER_RF_EULER (ReflowEulerSampler). */
+ *    them refuses both with its "unknown kind" errors): ADF_PRECOND_RF / ADF_PRECOND_RF_EDM (ReFlow) and ADF_SAMPLER_RF_EULER (ReflowEulerSampler).
+ *    Added without a bump (new symbols only): adf_diffusion_loss with the three ADF_LOSS_* kinds, and adf_loss_calls -- a counter of its own,
+ *    because adf_run_counters must not grow within a version. */
 #define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
@@ -229,6 +231,30 @@ int adf_net_forward(adf_handle* h, const float* x, const float* t, float* out, i
 int adf_denoise(adf_handle* h, const float* x_noisy, const float* sigmas_dev, float sigma, float sigma_data,
                 float* out, int B, int L, void* stream);
 
+/* The validation loss: Diffusion.forward / VPDiffusion.forward / ReFlow.forward under torch.no_grad() (src/models/components/diffusion.py:65-97,
+ * :185-218, :420-442; called from diffunet_complex_module.py:116-125) as one call.  x, noise: [B][C][L] fp32, contiguous, 4-byte aligned;
+ * sigmas_dev: [B] on the device (sigmas for the x0 kinds -- VPDiffusion's already mapped from t -- and times t for ADF_LOSS_RF); losses: [B] fp32.
+ * Enqueues, in order:
+ *   mix      x_noisy = fl(x + fl(s_b noise)) (x0 kinds) or fl(fl(fl(1 - t_b) x) + fl(t_b noise)) (RF): every operation rounded to fp32 on its own, so
+ *            bit-equal to the reference's tensor expressions evaluated in fp32
+ *   denoise  exactly what adf_denoise(h, x_noisy, sigmas_dev, 0, sigma_data, pred, B, L, stream) enqueues, with the handle's preconditioning, clipping and
+ *            condition / guidance state (for ADF_LOSS_RF the handle is expected to be set to ADF_PRECOND_RF: pred is the raw velocity)
+ *   loss     losses[b] = w(s_b) / N * sum_i fl(d_i d_i), N = C * L; d = fl(pred - x) with w = (s^2 + sd^2) / (s sd)^2 (ADF_LOSS_X0_EDM) or 1 / s^2
+ *            (ADF_LOSS_X0_INV_SIGMA2); d = fl(fl(noise - x) - pred) with w = 1 (ADF_LOSS_RF).  Summed in double in a fixed order (no atomics: the same
+ *            bits on every run and every device), w / N formed in double from the fp32 sigma, one rounding to fp32.
+ * x_noisy_out / pred_out may each be NULL; if given they receive the noisy input and the denoiser output of this call ([B][C][L]; an output that
+ * overlaps x, noise or the other output is refused).  The handle needs in_channels == out_channels; a 2-D handle needs adf_set_image_shape first, a class-conditional one adf_set_condition.
+ * Refuses (adf_last_error names the argument) a null x, noise, sigmas_dev or losses, an unknown kind, sigma_data <= 0 for ADF_LOSS_X0_EDM.
+ * adf_run_counters is left as it is, every field (neither denoise_calls nor net_passes counts the loss's evaluation); adf_loss_calls counts the successful calls and is how a caller tells that the device path ran.
+ * The first loss call on a (B, L) workspace allocates; after it the call neither allocates nor synchronises and can be captured into the caller's graph
+ * (which then holds addresses of that workspace: replay it only while its (B, L) is among the 4 workspaces the handle keeps). */
+#define ADF_LOSS_X0_EDM        0   /* EluDiffusion  diffusion.py:65-97, :243-245 */
+#define ADF_LOSS_X0_INV_SIGMA2 1   /* VEDiffusion :118-120, VPDiffusion :152-154 (sigmas already mapped from t, :185-218) */
+#define ADF_LOSS_RF            2   /* ReFlow(for_edm=False) :420-442 */
+int adf_diffusion_loss(adf_handle* h, int kind, const float* x, const float* noise, const float* sigmas_dev, float sigma_data,
+                       float* losses, float* x_noisy_out, float* pred_out, int B, int L, void* stream);
+int64_t adf_loss_calls(const adf_handle* h);   /* successful adf_diffusion_loss calls */
+
 /* Full sampling loop.  sigmas_host: the schedule tensor (host, n_sigmas entries) the reference passes as
  * `sigmas`; noise: unit-variance [B][C][L]; injected_noise: [n_injected][B][C][L] draws replacing
  * randn_like, one per step in the reference's order (required when the EDM / DPM2 sampler churns and always for
@@ -290,6 +316,12 @@ int adf_bench_layer(adf_handle* h, int B, int L, int level, int conv, int iters,
  * on `stream`.  The working set of one launch at bench sizes (y, y_next, fp32 skip sum: > 5 GB at B = 128, T = 22050) is far beyond
  * the 256 MiB Infinity Cache, so no operand rotation is needed. */
 int adf_bench_wavenet_layer(adf_handle* h, int B, int T, int layer, int iters, float* ms, double* algo_bytes, double* flops, void* stream);
+
+/* The two memory-bound kernels of adf_diffusion_loss alone (any handle; its network is not run): the mix and the per-block squared-error sums over
+ * B rows of N fp32 elements in buffers of their own, `iters` launches each after 2 untimed ones, with HIP events on `stream`.  rf != 0: the ADF_LOSS_RF
+ * forms (the error pass then reads the noise too).  *bytes_* = the tensor traffic of one launch.  Allocates and frees 16 B N bytes per call. */
+int adf_bench_loss_kernels(adf_handle* h, int rf, int B, long long N, int iters, float* ms_mix, float* ms_partial, double* bytes_mix,
+                           double* bytes_partial, void* stream);
 
 /* SpecToWave: the tail of DiffUnetComplexModule.synthesize_from_noise (src/models/diffunet_complex_module.py:90-99) in one launch --
  * view_as_complex(permute(spec)) + spec_back (src/models/utils.py:22-28) + torch.istft(window, normalized, center=True, length=None).
