@@ -45,7 +45,19 @@ struct GemmSeg {
     const void* w;      // packed [nchunk][taps][n_pad][row of 128 B]
     const void* wfrag;  // optional second copy in MFMA-fragment order [K step][2][n_pad][8] (bf16; adf_gemm_tile.h)
     int nchunk;
+    int tap2_zero_c;    // 3 taps of a folded strided conv: > 0 = the first channel from which the weights of tap 2 are zero by construction (taps 0 and 1 fully real)
 };
+
+// Strided Conv1d(K, stride f) over C channels folded to stride 1 over f C channels (pack_weight mode 2): slot j of folded tap t' carries kernel tap t' f + j,
+// real iff that is < K.  With three folded taps of which taps 0 and 1 are real everywhere: the first folded channel from which tap 2 is zero
+// (GemmSeg::tap2_zero_c), when whole 64-channel K blocks are; else 0
+inline int folded_tap2_zero_from(int K, int f, int C) {
+    if (f < 1 || C < 1 || (K - 1) / f + 1 != 3) return 0;
+    int z = f;
+    for (int j = f - 1; j >= 0 && 2 * f + j >= K; --j) z = j;      // the zero slots of tap 2 are its last ones
+    if (z == 0 || z == f || f + (f - 1) >= K) return 0;
+    return (z * C) % 64 == 0 ? z * C : 0;
+}
 
 struct GemmArgs {
     GemmSeg seg[2];

@@ -191,9 +191,10 @@ bool rb_tiles(const GemmArgs& a, const RbForm& f, long long min_tiles, RbTiles& 
     return t.total <= (1 << 22) && t.total >= min_tiles;
 }
 
-// the K-block table of one tile and the argument head, for a shape that rb_shape_ok and rb_tiles accepted
+// the K-block table of one tile and the argument head, for a shape that rb_shape_ok and rb_tiles accepted.  zskip (bf16 form, raw launches): leave out the
+// sub-steps whose weights are zero by construction -- RbHead::nb2 / phase2
 template <typename ArgsT>
-void rb_fill_args(const GemmArgs& a, const RbForm& f, const RbTiles& t, ArgsT& r) {
+void rb_fill_args(const GemmArgs& a, const RbForm& f, const RbTiles& t, int zskip, ArgsT& r) {
     const GemmSeg& g0 = a.seg[0];
     memset(&r, 0, sizeof(r));
     int nb = 0;
@@ -213,6 +214,17 @@ void rb_fill_args(const GemmArgs& a, const RbForm& f, const RbTiles& t, ArgsT& r
     if (a.nseg > 1) add_seg(a.seg[1].src0, a.seg[1].src1, a.seg[1].c0, a.seg[1].c1, a.seg[1].w, 1, false, a.seg[1].scale1);
     r.h.res = a.nseg == 1 ? a.res : nullptr;                             // identity residual: added in the epilogue (fp32, before the rounding)
     r.h.nb1 = nb - r.h.nb3;
+    if (zskip && rb_raw0(a)) {
+        // folded strided conv: tap 2 is zero from folded channel tap2_zero_c on.  Two-tap blocks only behind an even number (the two-stage ring's parity) of at
+        // least two (a tile starts with a three-tap block) three-tap blocks; else the table stays as it was
+        const int z = g0.tap2_zero_c, nbz = z / f.blk_ch;
+        if (!a.phase_c && z > 0 && z % f.blk_ch == 0 && nbz >= 2 && nbz % 2 == 0 && nbz < r.h.nb3) {
+            r.h.nb2 = r.h.nb3 - nbz;
+            r.h.nb3 = nbz;
+        }
+        // x2 transposed conv in its 3-tap form: the N halves are the phases
+        if (a.phase_c && a.n == 2 * a.phase_c && t.nh == 2) r.h.phase2 = 1;
+    }
     r.h.B = a.B; r.h.L = a.mrows;
     r.h.n = a.n;
     r.h.gn = g0.gn;
@@ -228,18 +240,24 @@ void rb_fill_args(const GemmArgs& a, const RbForm& f, const RbTiles& t, ArgsT& r
 }
 
 // Resblock conv kernel (adf_gemm_rb.h): one 512-thread block per CU.
-const char* launch_rb(const GemmArgs& a, long long min_tiles, hipStream_t stream) {
+const char* launch_rb(const GemmArgs& a, long long min_tiles, int zskip, hipStream_t stream) {
     RbTiles t;
     RbArgs r;
     rb_tiles(a, kRbBf16, min_tiles, t);
-    rb_fill_args(a, kRbBf16, t, r);
+    rb_fill_args(a, kRbBf16, t, zskip, r);
+    if (r.h.nb2 && (r.h.nb3 < 2 || r.h.nb3 % 2 || r.h.nb1)) return "conv_gemm_rb: two-tap blocks need an even number >= 2 of three-tap blocks ahead of them";
     if (!raise_lds_limit<kRbLds, conv_gemm_rb_kernel<1, false, 2>, conv_gemm_rb_kernel<2, false, 2>, conv_gemm_rb_kernel<1, true, 2>, conv_gemm_rb_kernel<2, true, 2>,
                          conv_gemm_rb_kernel<1, false, 1>, conv_gemm_rb_kernel<2, false, 1>, conv_gemm_rb_kernel<1, true, 1>, conv_gemm_rb_kernel<2, true, 1>>())
         return "hipFuncSetAttribute(MaxDynamicSharedMemorySize, rb) failed";
     const long long grid = t.total < device_cus() ? t.total : device_cus();
     const bool raw0 = rb_raw0(a);
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), kRbLds, stream, r); };
-    if (t.tm == 256) {
+    if (r.h.phase2) {
+        if (!raise_lds_limit<kRbLds, conv_gemm_rb_kernel<2, true, 2, true>, conv_gemm_rb_kernel<2, true, 1, true>>())
+            return "hipFuncSetAttribute(MaxDynamicSharedMemorySize, rb) failed";
+        if (t.tm == 256) go(conv_gemm_rb_kernel<2, true, 2, true>);
+        else go(conv_gemm_rb_kernel<2, true, 1, true>);
+    } else if (t.tm == 256) {
         if (t.nh == 2 && raw0) go(conv_gemm_rb_kernel<2, true, 2>);
         else if (t.nh == 2) go(conv_gemm_rb_kernel<2, false, 2>);
         else if (raw0) go(conv_gemm_rb_kernel<1, true, 2>);
@@ -258,7 +276,7 @@ const char* launch_rbx3(const GemmArgs& a, long long min_tiles, hipStream_t stre
     RbTiles t;
     Rbx3Args r;
     rb_tiles(a, kRbX3, min_tiles, t);
-    rb_fill_args(a, kRbX3, t, r);
+    rb_fill_args(a, kRbX3, t, 0, r);
     if (!raise_lds_limit<kRbLds, conv_gemm_rbx3_kernel<2>, conv_gemm_rbx3_kernel<1>>()) return "hipFuncSetAttribute(MaxDynamicSharedMemorySize, rbx3) failed";
     const long long grid = t.total < device_cus() ? t.total : device_cus();
     if (t.tm == 256) hipLaunchKernelGGL(conv_gemm_rbx3_kernel<2>, dim3((unsigned)grid), dim3(512), kRbLds, stream, r);
@@ -342,6 +360,7 @@ struct GemmSwitches {
     // the other routes (A/B; the tests compare the two), = 2 takes small batches too (tests)
     long long rb_min_tiles = min_tiles_of(adf_route_switch("ADF_GEMM_RB", 1));
     long long rbx3_min_tiles = min_tiles_of(adf_route_switch("ADF_GEMM_RBX3", 1));
+    int rb_zskip = adf_route_switch("ADF_RB_ZSKIP", 1);     // 0: the raw launches of the resblock conv kernel run their structurally zero sub-steps too (A/B; the tests compare the two)
     int gn_in_kernel = (int)adf_tuning("ADF_GEMM_GN", 1);               // 0: always launch gn_finalize (A/B)
     int min_blocks = (int)adf_tuning("ADF_GEMM_MINBLOCKS", 512);        // the generic kernel's tiles shrink until the grid has this many blocks
     int ksplit = (int)adf_tuning("ADF_GEMM_KSPLIT", 1);                 // 0: off; 32: 32 x 32 tiles only
@@ -610,7 +629,7 @@ const char* launch_conv_gemm(const GemmArgs& a_in, int dtype, hipStream_t stream
         if (p.tm == 64) return dtype == 1 ? launch_ksplit<bf16_t, 2, 2>(a, stream) : (dtype == 2 ? launch_ksplit<f32x3_t, 2, 2>(a, stream) : launch_ksplit<float, 2, 2>(a, stream));
         return dtype == 1 ? launch_ksplit<bf16_t, 1, 1>(a, stream) : (dtype == 2 ? launch_ksplit<f32x3_t, 1, 1>(a, stream) : launch_ksplit<float, 1, 1>(a, stream));
     case Route::rbx3: return launch_rbx3(a, sw.rbx3_min_tiles, stream);
-    case Route::rb: return launch_rb(a, sw.rb_min_tiles, stream);
+    case Route::rb: return launch_rb(a, sw.rb_min_tiles, sw.rb_zskip, stream);
     case Route::pp: return p.tm == 256 ? launch_pp<2>(a, stream) : launch_pp<1>(a, stream);
     case Route::ws:
         if (p.tn == 128) return dtype == 1 ? launch_ws_variant<bf16_t, 2, 2>(a, stream) : launch_ws_variant<float, 2, 2>(a, stream);
@@ -620,6 +639,33 @@ const char* launch_conv_gemm(const GemmArgs& a_in, int dtype, hipStream_t stream
 }
 
 }  // namespace adf
+
+// include/audiodiffuser_amd.h: the K-block table launch_rb would build for a raw launch (host arithmetic only)
+extern "C" int adf_debug_rb_block_plan(int K, int f, int C, int phase_c, int n, int B, int L, int min_tiles, int zskip, int* tile_rows, int* nh, int* nb3, int* nb2,
+                                       int* phase2) {
+    using namespace adf;
+    if (B < 1 || L < 1 || C < 1 || f < 1 || (long long)B * L > 0x3fffffffLL) return 1;
+    static const char dummy[16] = {};
+    GemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nseg = 1; a.B = B; a.lin = a.mrows = a.out_rows = L; a.n = a.n_pad = a.out_c = a.bias_mod = n;
+    a.phase_c = phase_c;
+    GemmSeg& g = a.seg[0];
+    g.src0 = g.w = dummy;
+    g.c0 = phase_c ? C : f * C;
+    g.taps = 3; g.stride = 1; g.off0 = -1; g.step = 1;
+    g.tap2_zero_c = phase_c ? 0 : folded_tap2_zero_from(K, f, C);
+    RbTiles t;
+    if (!rb_shape_ok(a, kRbBf16, false) || !rb_tiles(a, kRbBf16, min_tiles, t)) return 1;
+    RbArgs r;
+    rb_fill_args(a, kRbBf16, t, zskip, r);
+    if (tile_rows) *tile_rows = t.tm;
+    if (nh) *nh = t.nh;
+    if (nb3) *nb3 = r.h.nb3;
+    if (nb2) *nb2 = r.h.nb2;
+    if (phase2) *phase2 = r.h.phase2;
+    return 0;
+}
 
 // include/audiodiffuser_amd.h: the tile plan launch_up would take for one of the four shapes of the transposed-conv kernel (host arithmetic only)
 extern "C" int adf_debug_up_tile_plan(int cin, int cout, int f, int B, int L, int* tile_rows, int* items, int* rounds, int* dead_rows) {

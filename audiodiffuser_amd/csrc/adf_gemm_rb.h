@@ -107,7 +107,7 @@ struct RbBlk {
 // by field where first used, the kernel arguments were ~12 serialised scalar-cache round trips ahead of the first DMA -- ~7 K cycles
 // from wave start to the first DMA instruction, profiles/r03_rb_launch_timeline.txt).
 struct RbHead {
-    int nb3, nb1;             // K blocks of one tile, in order: nb3 three-tap blocks (GroupNorm + SiLU), then nb1 one-tap raw blocks
+    int nb3, nb1;             // K blocks of one tile, in order: nb3 three-tap blocks (GroupNorm + SiLU), [nb2 two-tap blocks, below,] then nb1 one-tap raw blocks
     int B, L;                 // samples, rows per sample
     int tm_shift;             // log2(block tiles (256 or 128 rows) per sample)
     int tiles_n;              // N tiles (1 or 2), N tile index fastest
@@ -119,6 +119,11 @@ struct RbHead {
     const void* res;          // identity residual (same layout as out), added in the epilogue in fp32 before the rounding, or nullptr
     double* stats; int stats_groups;
     int stats_mod;            // 0, or the channels of one phase of a transposed conv in its 3-tap form: column n is channel n % stats_mod (a power of two >= 64)
+    // Structurally zero taps of the raw launches (bf16 form only; both 0 = every block three-tap).  Nothing is repacked: a block's slabs stay [tap][n][64 ch].
+    int nb2;                  // two-tap blocks between the three-tap and the one-tap blocks: tap 2 of a folded strided conv is zero for them, its slab is never fetched
+    int phase2;               // 3-tap form of a x2 transposed conv on 256-column tiles: N half = phase, (tap 2, half 0) and (tap 0, half 1) are zero -- four sub-steps
+                              // per block, (tap (v + 1) / 2, half v / 2).  (On 128-column tiles the two wave columns are the phases: a form in which they skipped
+                              // the MFMAs of their zero tap, DMAs and barriers as they are, measured no faster -- DESIGN.md section 4 -- and is not kept.)
 };
 struct RbArgs {
     RbHead h;
@@ -151,8 +156,11 @@ __device__ __forceinline__ void rb_static_for(F&& f) {
 // MH = 32-row accumulator tiles per wave: 2 -> 256-row block tiles, 1 -> 128-row tiles for the levels whose 256-row tile count leaves CUs idle
 // (L = 256 at batch 64: round 3, these launches ran on adf_gemm_pp.h's 128-row form before -- profiles/r03_pp_launch_timeline_L256.txt).  The
 // LDS layout is the same (a 128-row block uses the first half of a stage, halo piece behind it).
-template <int NH, bool RAW, int MH = 2>
+// PHASE (RAW only; the launcher picks it from RbHead::phase2): the phase form of a x2 transposed conv.  A kernel of its own, not a run-time branch: with both
+// block loops in one kernel the allocator moved the accumulators of the 256 x 256 form through scratch (435 spilled VGPRs).
+template <int NH, bool RAW, int MH = 2, bool PHASE = false>
 __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
+    static_assert(!PHASE || (RAW && NH == 2), "the phase form: no prologue, N half = phase");
     typedef bf16_t T;
     constexpr int TM = 128 * MH, HP = TM / 8;            // HP: piece index of the halo rows TM, TM + 1 -- they follow row TM - 1 in the stage
     constexpr int TNB = kPpTN * NH;                      // columns of the block tile
@@ -192,7 +200,9 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
     const int t_hi = (int)((unsigned)(bidx + 1) * (unsigned)H.tiles_total / (unsigned)nblk_grid);
     const int ntiles = t_hi - t_lo;
     if (ntiles <= 0) return;
-    const int nb3 = H.nb3, nb1 = H.nb1, nb = nb3 + nb1;
+    // (the zero-tap forms exist in the RAW kernels only: the others fold nb2 / phase2 away and compile to what they were)
+    const int nb3 = H.nb3, nb2 = RAW ? H.nb2 : 0, nb1 = H.nb1, nbh = nb3 + nb2, nb = nbh + nb1;
+    constexpr bool phase2 = PHASE;                     // every block of the launch has the four phase sub-steps
     const int ctot0 = H.gn.c0 + H.gn.c1;
     const int tn_shift = H.tiles_n > 1 ? 1 : 0;
     const int tm_mask = (1 << H.tm_shift) - 1;
@@ -228,14 +238,14 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
     Tile d_tile = tile_of(0);
     auto make_desc_of = [&](const RbBlk& e) __attribute__((always_inline)) -> Blk {
         Blk d;
-        const int three = d_k < nb3;
+        const int three = d_k < nbh;                   // a block with a halo: three taps, or two taps + a zero third (`taps` = its sub-steps / NH)
         const int p_lo = d_tile.m0 - three;
         d.pitch = e.pitch;
         d.abase = e.src + (long long)(d_tile.b0 * H.L + p_lo) * (long long)e.pitch;
         d.w = e.w + (unsigned)d_tile.n0 * (unsigned)kRowBytes;
         d.tab = e.tab >= 0 ? ((d_tile.b0 - b_first) & 1) * kPpTab + e.tab : -1;
         d.scale = e.scale;
-        d.taps = three ? 3 : 1;
+        d.taps = three ? ((d_k < nb3 && !phase2) ? 3 : 2) : 1;
         d.edge = three ? ((d_tile.m0 == 0 ? 1 : 0) | (d_tile.m0 + TM >= H.L ? 2 : 0)) : 0;
         return d;
     };
@@ -247,6 +257,11 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
         }
     };
     const unsigned slab = (unsigned)H.n * (unsigned)kRowBytes;           // one tap of packed weights
+    // the slab of sub-step v of block d: (tap v / NH, N half v % NH); phase2: (tap 0, half 0), (1, 0), (1, 1), (2, 1)
+    auto slab_of = [&](const Blk& d, int v) __attribute__((always_inline)) -> const char* {
+        const int tap = phase2 ? (v + 1) >> 1 : v / NH, hf = phase2 ? v >> 1 : v % NH;
+        return d.w + (unsigned)tap * slab + (unsigned)hf * (unsigned)kPpWStage;
+    };
 
     // ---- DMA ----------------------------------------------------------------------------------------------------
     const unsigned colbytes = (unsigned)chunk * 16u;
@@ -266,7 +281,7 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
     };
     auto issue_halo = [&](const Blk& d, unsigned st) __attribute__((always_inline)) {
         if (ADF_RB_KNOCK & 2) return;
-        if (wave == 0 && d.taps == 3) {
+        if (wave == 0 && d.taps > 1) {
             // rows TM, TM + 1 of the tile; past the end of the sample both lane rows fetch row TM (zeroed later)
             const unsigned vh = (unsigned)TM * d.pitch + ((d.edge & 2) ? 0u : (unsigned)lrow * d.pitch) + colbytes;
             if (lane < 16) rb_dma1(d.abase, vh, st + (unsigned)HP * 1024u);
@@ -405,7 +420,7 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
             return;
         }
         char* const ldsH = smem + st + HP * 1024 + lane_lds;
-        const bool halo = wave == 0 && d.taps == 3 && lane < 16;
+        const bool halo = wave == 0 && d.taps > 1 && lane < 16;
         const bool act = true;
         float fa[8], fb[8];
         load_ab(d, 0, 8, fa, fb);
@@ -552,7 +567,7 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
                 case 6: p.hx = p.hx * p.hu; break;
                 default:
                     // row TM + 1 past the end of the sample is zeroed by wave 0 (zero_fill): its owners (waves 4-7) leave it alone
-                    if (dn.taps == 3 && !((dn.edge & 2) && wave >= 4)) {                      // uniform
+                    if (dn.taps > 1 && !((dn.edge & 2) && wave >= 4)) {                      // uniform
                         if (lane < 16) *(unsigned short*)(smem + sn + HP * 1024 + halo_e * 2u) = (unsigned short)pack_bf16x2(p.hx, p.hx);
                     }
                     break;
@@ -767,7 +782,7 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
     advance();
     issue_a01(dc, 0u); issue_a23(dc, 0u); issue_halo(dc, 0u);
     issue_w(dc.w, 0);
-    if (W3 && !ADF_RB_FILL2) issue_w(dc.w + (unsigned)(1 / NH) * slab + (unsigned)(1 % NH) * (unsigned)kPpWStage, 1);     // (a tile starts with a 3-tap block: its second sub-step)
+    if (W3 && !ADF_RB_FILL2) issue_w(slab_of(dc, 1), 1);     // (a tile starts with a 3-tap block: its second sub-step)
     Blk d1 = make_desc_of(e_first[1]);
     advance();
     if (!ADF_RB_FILL2) { issue_a01(d1, (unsigned)kPpAStage); issue_a23(d1, (unsigned)kPpAStage); issue_halo(d1, (unsigned)kPpAStage); }
@@ -784,7 +799,7 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
     tl(1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (ADF_RB_FILL2) {
-        if (W3) issue_w(dc.w + (unsigned)(1 / NH) * slab + (unsigned)(1 % NH) * (unsigned)kPpWStage, 1);
+        if (W3) issue_w(slab_of(dc, 1), 1);
         issue_a01(d1, (unsigned)kPpAStage); issue_a23(d1, (unsigned)kPpAStage); issue_halo(d1, (unsigned)kPpAStage);
     }
     __syncthreads();
@@ -817,6 +832,7 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
     const std::integral_constant<int, 0> c0{};
     const std::integral_constant<int, 1> c1{};
     const std::integral_constant<int, 2> c2{};
+    const std::integral_constant<int, 3> c3{};
     auto lds_barrier = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     auto rotate = [&]() __attribute__((always_inline)) {
         const unsigned t = sa; sa = sa1; sa1 = sa2; sa2 = t;
@@ -832,15 +848,9 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
     // the slabs of sub-steps 0 (halo, pieces 0-1) and 1 (pieces 2-3): spread over time, a slab is never queued behind more
     // than two HBM pieces of its own wave (tools/micro/dma_mix.hip: the two streams share the CU's miss slots, they do not
     // overlap), and the end-of-sub-step wait leaves exactly the pieces issued in that sub-step in flight.
-    auto next_slab = [&](int u, int taps_) __attribute__((always_inline)) -> const char* {
-        return dc.w + (unsigned)(u / NH) * slab + (unsigned)(u % NH) * (unsigned)kPpWStage;
-    };
     // ---- W3: the slab TWO sub-steps ahead, and counted waits ----------------------------------------------------------------------
     // v = index of that sub-step counted from the first sub-step of the current block (ucur of them), running on into block g+1 and,
     // behind a one-sub-step block, g+2.  Returns the number of DMA instructions issued (2 or 0).
-    auto slab_of = [&](const Blk& d, int v) __attribute__((always_inline)) -> const char* {
-        return d.w + (unsigned)(v / NH) * slab + (unsigned)(v % NH) * (unsigned)kPpWStage;
-    };
     auto issue_ahead = [&](int v, int ucur, bool has1, bool has2) __attribute__((always_inline)) -> int {
         if (v < ucur) { issue_w_at(slab_of(dc, v), ws2); return 2; }
         v -= ucur;
@@ -879,10 +889,17 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
     int epi_vm = 0;
     bool slab1_pre = false;                            // two-stage ring: the slab of the tile's second sub-step went out ahead of the epilogue
     int aq_prev = 0;                                   // activation DMAs this wave issued in the previous sub-step (behind its slab)
-    // one 3-tap block whose first sub-step reads W stage WP; the prologue of block g+1 (any kind) rides in its gaps
-    auto block3 = [&](auto wpc) __attribute__((always_inline)) {
+    // one block with a halo whose first sub-step reads W stage WP; the prologue of block g+1 (any kind) rides in its gaps.  TAPS = 3, or (RAW only: with
+    // nothing in the gaps a shorter block starves no prologue) 2 = the block's third tap is zero and left out; PH (NH = 2) = the four sub-steps of a phase2
+    // block.  Every sub-step that remains issues what it issued before -- the slab ahead, block g+2's halo + pieces 0-1 in u = 0, pieces 2-3 in u = 1 -- so the
+    // counted waits hold as they are; a two-tap block has an even number of sub-steps on the two-stage ring and leaves its parity where it found it.
+    auto block3 = [&](auto wpc, auto tapsc, auto phc) __attribute__((always_inline)) {
         constexpr int WP = decltype(wpc)::value;
-        constexpr int U = 3 * NH;
+        constexpr int TAPS = decltype(tapsc)::value;
+        constexpr bool PH = decltype(phc)::value != 0;
+        static_assert(TAPS == 3 || (RAW && TAPS == 2), "a block with a prologue behind it has three sub-steps per N half");
+        static_assert(!PH || (RAW && NH == 2 && TAPS == 2), "the phase sub-steps: raw 256-column tiles");
+        constexpr int U = TAPS * NH;
 #ifdef ADF_RB_STAMP
         const bool stamp_on = bidx == 0 && tseq == 1 && kb == 2 && WP == 0;
         auto stamp = [&](int id) __attribute__((always_inline)) {
@@ -902,7 +919,7 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
         stamp(0);
         rb_static_for<0, U>([&](auto uc) __attribute__((always_inline)) {
             constexpr int u = decltype(uc)::value;
-            constexpr int TAP = u / NH, HF = u % NH;
+            constexpr int TAP = PH ? (u + 1) / 2 : u / NH, HF = PH ? u / 2 : u % NH;           // (slab_of)
             const std::integral_constant<int, TAP> tapc{};
             const std::integral_constant<int, (WP + u) & 1> wstc{};
             const std::integral_constant<int, HF> hfc{};
@@ -912,10 +929,10 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
                     [&](int ks) __attribute__((always_inline)) {
                         if (ks == 0) {
                             if (W3) wq = issue_ahead(u + 2, U, has1, has2);
-                            else if (u + 1 < U) { if (!(u == 0 && slab1_pre)) issue_w(next_slab(u + 1, 3), (WP + u + 1) & 1); }
+                            else if (u + 1 < U) { if (!(u == 0 && slab1_pre)) issue_w(slab_of(dc, u + 1), (WP + u + 1) & 1); }
                             else if (has1) issue_w(d1.w, (WP + u + 1) & 1);
                         } else if (ks == 1 && has2) {
-                            if (u == 0) { issue_halo(d2, sa2); issue_a01(d2, sa2); aq = (wave == 0 && d2.taps == 3) ? 3 : 2; }
+                            if (u == 0) { issue_halo(d2, sa2); issue_a01(d2, sa2); aq = (wave == 0 && d2.taps > 1) ? 3 : 2; }
                             else if (u == 1 && MH == 2) { issue_a23(d2, sa2); aq = 2; }
                         }
                     });
@@ -968,12 +985,12 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
                     [&](int ks) __attribute__((always_inline)) {
                         if (ks == 0) {
                             if (W3) wq = issue_ahead(u + 2, NH, has1, has2);
-                            else if (u + 1 < NH) issue_w(next_slab(u + 1, 1), (WP + u + 1) & 1);
+                            else if (u + 1 < NH) issue_w(slab_of(dc, u + 1), (WP + u + 1) & 1);
                             else if (has1) issue_w(d1.w, (WP + u + 1) & 1);
                         } else if (u == NH - 1 && has2) {
                             if (ks == 1) { issue_a01(d2, sa2); aq += 2; }
                             else if (ks == 2) { issue_a23(d2, sa2); if (MH == 2) aq += 2; }
-                            else { issue_halo(d2, sa2); if (wave == 0 && d2.taps == 3) aq += 1; }
+                            else { issue_halo(d2, sa2); if (wave == 0 && d2.taps > 1) aq += 1; }
                         }
                     });
             if (W3) {
@@ -986,8 +1003,8 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
             } else if (u == NH - 1) {
                 // block g+1's activations (issued one block ago) and its first slab have landed; block g+2's may still fly
                 if (has2) {
-                    if (MH == 2) { if (wave == 0 && d2.taps == 3) asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-                    else { if (wave == 0 && d2.taps == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
+                    if (MH == 2) { if (wave == 0 && d2.taps > 1) asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
+                    else { if (wave == 0 && d2.taps > 1) asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
                 }
                 else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (has1) transform_all(d1, sa1);
@@ -1015,7 +1032,7 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
                 //  head of the first block on -- the wait block3 does for that, taken here, ahead of the epilogue's stores)
                 if (prev_one) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); aq_prev = 0; prev_one = false; }
                 // (two-stage ring: the stage the second sub-step's slab goes to was read last by the finished tile's last sub-step, whose barrier has passed)
-                if (!W3) { issue_w(next_slab(1, 3), 1); slab1_pre = true; }
+                if (!W3) { issue_w(slab_of(dc, 1), 1); slab1_pre = true; }
                 epi_vm = NH * 4 * MH * (H.res != nullptr ? 2 : 1) + (H.stats != nullptr ? 2 * NH : 0);
             }
             epilogue(tile_of(tseq - 1), cur_tile.n0, sa2);       // (sa2: the stage of the previous tile's last block, not yet refilled)
@@ -1024,14 +1041,26 @@ __global__ void __launch_bounds__(512) conv_gemm_rb_kernel(const RbArgs a) {
         tl(4 + tseq * 26 + 1);
 #endif
         // blocks come in pairs (nb3 and nb1 are even): the weight stage parity is a compile-time constant
-        for (kb = 0; kb < nb3; kb += 2) {
-            block3(c0); rotate(); --remaining; prev_one = false;
-            block3(std::integral_constant<int, kPar3>{}); rotate(); --remaining;
+        if constexpr (phase2) {
+            // four sub-steps per block, an even number: the parity stays 0 on a two-stage ring
+#pragma nounroll
+            for (kb = 0; kb < nb3; ++kb) { block3(c0, c2, c1); rotate(); --remaining; }
+        } else {
+            for (kb = 0; kb < nb3; kb += 2) {
+                block3(c0, c3, c0); rotate(); --remaining; prev_one = false;
+                block3(std::integral_constant<int, kPar3>{}, c3, c0); rotate(); --remaining;
+            }
+            // two-tap blocks (the host builds them only behind an even number of three-tap blocks): the parity stays 0 on the two-stage ring
+            if constexpr (RAW)
+#pragma nounroll
+                for (; kb < nbh; ++kb) { block3(c0, c2, c0); rotate(); --remaining; }
         }
-        for (int k1 = 0; k1 < nb1; k1 += 2) {
-            block1(c0); rotate(); --remaining;
-            block1(std::integral_constant<int, kPar1>{}); rotate(); --remaining; prev_one = true;
-        }
+        // (a raw launch has one segment -- rb_shape_ok: no one-tap blocks)
+        if constexpr (!RAW)
+            for (int k1 = 0; k1 < nb1; k1 += 2) {
+                block1(c0); rotate(); --remaining;
+                block1(std::integral_constant<int, kPar1>{}); rotate(); --remaining; prev_one = true;
+            }
     }
     {
         const Tile last = tile_of(ntiles - 1);

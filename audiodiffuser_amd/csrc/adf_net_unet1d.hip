@@ -450,6 +450,7 @@ int Unet1dNet::forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
         xv.C = x.C * f; xv.L = x.L / f; xv.stats = nullptr;
         GemmArgs g = W.gemm_base(y, xv.L, y.L, d.down);
         g.seg[0] = Walker1d::seg_of(xv, nullptr, nullptr, 1.f, 0, km + 1, 1, -(km / 2), 1, d.down);
+        g.seg[0].tap2_zero_c = folded_tap2_zero_from(d.down.K, f, x.C);
         W.run_gemm(g, y, true);
         W.tap("down" + std::to_string(i) + ".conv", y);
         x = y;

@@ -53,7 +53,7 @@ extern "C" {
  *    style of adf_set_dynamic_threshold: adf_sampler_desc and the argument list of adf_denoise are unchanged, so a caller that fills only the
  *    fields of version 6 and never calls the setter still gets EluDiffusion's rows.
  *    Added without a bump (new symbols only, nothing of the above changes): adf_istft_config and the four adf_istft_* entry points;
- *    the four adf_stft_* entry points (WaveToSpec), which take the same adf_istft_config; adf_debug_tap_stats and adf_debug_up_tile_plan.
+ *    the four adf_stft_* entry points (WaveToSpec), which take the same adf_istft_config; adf_debug_tap_stats, adf_debug_up_tile_plan and adf_debug_rb_block_plan.
  *    Also without a bump (new values of existing int arguments / fields; no struct grows and no argument list changes, and a library of version 7 without
  *    them refuses both with its "unknown kind" errors): ADF_PRECOND_RF / ADF_PRECOND_RF_EDM (ReFlow) and ADF_SAMPLER_RF_EULER (ReflowEulerSampler).
  *    Added without a bump (new symbols only): adf_diffusion_loss with the three ADF_LOSS_* kinds, and adf_loss_calls -- a counter of its own,
@@ -275,6 +275,13 @@ int adf_debug_tap_stats(adf_handle* h, const char* name, double* out_host, int* 
  * one of its four shapes (cin -> cout, factor f): rows per tile, work items (sample x tile x column pass), rounds of 256 workgroups, and the
  * rows of a sample's last tile past L.  Returns nonzero for any other shape. */
 int adf_debug_up_tile_plan(int cin, int cout, int f, int B, int L, int* tile_rows, int* items, int* rounds, int* dead_rows);
+/* Host arithmetic only: the K-block table the resblock conv kernel's raw form (csrc/adf_gemm_rb.h, bf16) gets for B samples of L rows and n columns.
+ * phase_c = 0: Conv1d(K, stride f) over C channels folded to 3 taps over f C channels (L = output rows); phase_c > 0: the 3-tap form of a transposed
+ * conv over C channels with n / phase_c phases (K, f unused).  min_tiles: fewest workgroup tiles the route takes; zskip: the ADF_RB_ZSKIP switch.
+ * Out: rows per tile, 128-column halves per tile, three-tap and two-tap K blocks per tile, and whether the launch takes the phase form.  Returns
+ * nonzero for a shape the kernel does not take. */
+int adf_debug_rb_block_plan(int K, int f, int C, int phase_c, int n, int B, int L, int min_tiles, int zskip, int* tile_rows, int* nh, int* nb3, int* nb2,
+                            int* phase2);
 /* The dynamic threshold alone, in place on x_dev [B][per_sample] (tests: exactness of the order statistics against torch.quantile). */
 int adf_debug_dyn_threshold(adf_handle* h, float* x_dev, int B, long long per_sample, float quantile, void* stream);
 /* The (c_in, c_noise, c_skip, c_out) rows of the last adf_sampler_run on this handle, one per denoiser evaluation in order: copies
