@@ -60,6 +60,26 @@ def make_sampler_desc(kind: int, num_steps: int, sigma_data: float, use_graph: b
                           **{"s_noise": 1.0, "alpha": 1.0, **fields})
 
 
+CLIP_NONE, CLIP_CONFIGURED, CLIP_UNIT = 0, 1, 2      # ADF_CLIP_* (adf_table_eval.clip)
+
+
+class AdfTableEval(C.Structure):
+    """``adf_table_eval`` of include/audiodiffuser_amd.h: the row of one denoiser evaluation and how it ends."""
+    _fields_ = [("c_in", C.c_float), ("c_noise", C.c_float), ("c_skip", C.c_float), ("c_out", C.c_float), ("clip", C.c_int32)]
+
+
+class AdfTableStep(C.Structure):
+    """``adf_table_step``: one record of the table-driven loop (``adf_sampler_run_table``)."""
+    _fields_ = [("a0", C.c_float), ("a1", C.c_float), ("eval1", AdfTableEval),
+                ("b0", C.c_float), ("b1", C.c_float), ("b2", C.c_float), ("second", C.c_int32), ("eval2", AdfTableEval),
+                ("c0", C.c_float), ("c1", C.c_float), ("c2", C.c_float), ("c3", C.c_float), ("draw", C.c_int32)]
+
+
+class AdfTableDesc(C.Structure):
+    """``adf_table_desc``."""
+    _fields_ = [("num_steps", C.c_int32), ("x0_scale", C.c_float), ("final_clamp", C.c_int32), ("use_graph", C.c_int32)]
+
+
 class AdfWaveNetConfig(C.Structure):
     """``adf_wavenet_config`` of include/audiodiffuser_amd.h."""
     _fields_ = [("residual_channels", C.c_int32), ("residual_layers", C.c_int32), ("dilation_cycle", C.c_int32),
@@ -141,6 +161,9 @@ EXPORTS = {
                                      C.c_int, C.c_int, C.c_void_p]),
     "adf_loss_calls": (C.c_int64, [C.c_void_p]),
     "adf_sampler_nfe": (C.c_int, [C.POINTER(AdfSamplerDesc), C.POINTER(C.c_float), C.c_int]),
+    "adf_sampler_run_table": (C.c_int, [C.c_void_p, C.POINTER(AdfTableDesc), C.POINTER(AdfTableStep), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                        C.c_int, C.c_int, C.c_void_p]),
+    "adf_sampler_table_nfe": (C.c_int, [C.POINTER(AdfTableDesc), C.POINTER(AdfTableStep)]),
     "adf_debug_tap_shape": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "adf_debug_tap_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]),
     "adf_debug_tap_stats": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

@@ -94,6 +94,121 @@ int create_finish(const char* fn, int dtype, std::unique_ptr<Net> net, adf_handl
     return 0;
 }
 
+// ---- what the two sampler entry points (adf_sampler_run, adf_sampler_run_table) share ------------------------------------------------------------
+// `floats` floats of injected noise copied into the plan's staging buffer, grown first where it is too small
+static int stage_injected(adf_handle* h, Plan* p, const float* injected_noise, size_t floats, hipStream_t s) {
+    if (p->inj_cap < floats) {
+        if (p->inj_stage) {                      // captured graphs read the old staging buffer: drain and drop them with it
+            (void)hipDeviceSynchronize();
+            drop_graphs(p);
+            dfree(h, p->inj_stage, p->inj_cap * 4, p);
+            p->inj_stage = nullptr; p->inj_cap = 0;
+        }
+        p->inj_stage = (float*)dalloc(h, floats * 4, p);
+        if (!p->inj_stage) return fail(h, "device allocation failed for injected noise");
+        p->inj_cap = floats;
+    }
+    if (hipMemcpyAsync(p->inj_stage, injected_noise, floats * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "injected-noise copy failed");
+    return 0;
+}
+
+// the buffers of the per-run table (Plan::coef_all / temb_all / film_all) for n_eval evaluations -- sized before any capture starts
+static int reserve_eval_tables(adf_handle* h, Plan* p, int n_eval) {
+    const NetDims& nd = h->net->dims;
+    p->pre_rows = n_eval;
+    if (n_eval <= p->pre_cap) return 0;
+    if (p->pre_cap) {
+        (void)hipDeviceSynchronize();
+        drop_graphs(p);
+        dfree(h, p->coef_all, (size_t)p->pre_cap * 4 * 4, p);
+        dfree(h, p->temb_all, (size_t)p->pre_cap * nd.temb * 4, p);
+        dfree(h, p->film_all, (size_t)p->pre_cap * h->film_total * 4, p);
+        p->pre_cap = 0;
+    }
+    p->coef_all = (float*)dalloc(h, (size_t)n_eval * 4 * 4, p);
+    p->temb_all = (float*)dalloc(h, (size_t)n_eval * nd.temb * 4, p);
+    p->film_all = (float*)dalloc(h, (size_t)n_eval * h->film_total * 4, p);
+    if (!p->coef_all || !p->temb_all || !p->film_all) return fail(h, "device allocation failed for the per-run sigma table");
+    p->pre_cap = n_eval;
+    return 0;
+}
+
+// sigma embeddings and FiLM projections of the n_eval rows already in Plan::coef_all, in two launches
+static int embed_eval_tables(adf_handle* h, Plan* p, int n_eval, hipStream_t st) {
+    const NetDims& nd = h->net->dims;
+    if (const char* e = h->net->time_embed(p->coef_all + 1, 4, n_eval, p->temb_all, st)) return fail(h, e);
+    if (h->per_sample_film()) return 0;                    // per-sample FiLM rows (time + class embedding): projected inside each pass
+    if (const char* e = launch_film(p->temb_all, nd.temb, h->film_w, nd.temb + h->cdim, 0, h->film_b, p->film_all, n_eval, h->film_total, st))
+        return fail(h, e);
+    return 0;
+}
+
+// the handle state a captured loop depends on, appended to its cache key
+static void append_handle_key(const adf_handle* h, std::string* key) {
+    key->push_back(h->cond_on ? 'c' : 'u');                   // the guidance branch structure is part of the captured graph
+    key->append((const char*)&h->cond_scale, sizeof(float));
+    key->append((const char*)&h->dyn_q, sizeof(float));        // the clipping of every evaluation is part of the captured graph
+    const Precond& pc = h->precond;                            // ... and so are the preconditioning formulas and their parameters
+    const float pk[6] = {(float)pc.kind, pc.beta_min2, pc.two_beta_d, pc.beta_min, pc.beta_d, pc.m_minus_1};
+    key->append((const char*)pk, sizeof(pk));
+}
+
+// One sampler run: enqueue(stream, &result) puts the whole loop on `stream` and names the buffer that holds the sample.  Eagerly on the caller's
+// stream, or -- use_graph -- captured once per `key` on the handle's own stream and replayed; then the copy to `out` and the counters.
+template <class Enqueue>
+static int run_loop(adf_handle* h, Plan* p, bool use_graph, const std::string& key, Enqueue enqueue, float* out, long long n, int n_eval, hipStream_t s) {
+    float* result = nullptr;
+    if (!use_graph) {
+        if (enqueue(s, &result)) return 1;
+        if (hipMemcpyAsync(out, result, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "result copy failed");
+        ++h->ctr.sampler_runs; h->ctr.sampler_evals += n_eval;
+        return 0;
+    }
+    if (!h->gstream) {
+        if (hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking) != hipSuccess ||
+            hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming) != hipSuccess)
+            return fail(h, "could not create the graph stream / events");
+    }
+    hipStream_t gs = h->gstream;
+    // inputs staged on the caller's stream must be visible to the graph stream
+    if (hipEventRecord(h->ev_in, s) != hipSuccess || hipStreamWaitEvent(gs, h->ev_in, 0) != hipSuccess)
+        return fail(h, "stream fence (in) failed");
+    auto it = std::find_if(p->graphs.begin(), p->graphs.end(), [&](const std::pair<std::string, hipGraphExec_t>& g) { return g.first == key; });
+    if (it != p->graphs.end() && it != p->graphs.begin()) {      // most recently used first
+        std::rotate(p->graphs.begin(), it, it + 1);
+        it = p->graphs.begin();
+    }
+    if (it == p->graphs.end()) {
+        const hipError_t be = hipStreamBeginCapture(gs, hipStreamCaptureModeRelaxed);
+        if (be != hipSuccess) return fail(h, std::string("hipStreamBeginCapture failed: ") + hipGetErrorString(be));
+        int rc = enqueue(gs, &result);
+        if (!rc && hipMemcpyAsync(p->out_stage, result, (size_t)n * 4, hipMemcpyDeviceToDevice, gs) != hipSuccess) { rc = 1; h->err = "result copy failed (capture)"; }
+        hipGraph_t graph = nullptr;
+        const hipError_t ee = hipStreamEndCapture(gs, &graph);
+        if (rc) { if (graph) (void)hipGraphDestroy(graph); return 1; }
+        if (ee != hipSuccess || !graph) return fail(h, std::string("hipStreamEndCapture failed: ") + hipGetErrorString(ee));
+        hipGraphExec_t exec = nullptr;
+        const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (ie != hipSuccess) return fail(h, std::string("hipGraphInstantiate failed: ") + hipGetErrorString(ie));
+        if (p->graphs.size() >= kMaxGraphsPerPlan) {               // every distinct (sampler, schedule, guidance) adds one: cap it
+            if (hipStreamSynchronize(gs) != hipSuccess) { (void)hipGraphExecDestroy(exec); return fail(h, "graph stream sync failed"); }
+            (void)hipGraphExecDestroy(p->graphs.back().second);
+            p->graphs.pop_back();
+        }
+        p->graphs.insert(p->graphs.begin(), std::make_pair(key, exec));
+        it = p->graphs.begin();
+        ++h->ctr.graph_captures;
+    }
+    if (hipGraphLaunch(it->second, gs) != hipSuccess) return fail(h, "hipGraphLaunch failed");
+    if (hipEventRecord(h->ev_out, gs) != hipSuccess || hipStreamWaitEvent(s, h->ev_out, 0) != hipSuccess)
+        return fail(h, "stream fence (out) failed");
+    if (hipMemcpyAsync(out, p->out_stage, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "result copy failed");
+    ++h->ctr.sampler_runs; ++h->ctr.graph_replays; h->ctr.sampler_evals += n_eval;
+    return 0;
+}
+
 }  // namespace adf_api
 
 // =====================================================================================================
@@ -350,118 +465,95 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
         // the ABI carries the number of [B][C][L] draws behind the pointer: a short buffer is an error, not an over-read
         if (n_injected < ndraws)
             return fail(h, "injected_noise holds " + std::to_string(n_injected) + " draws of [B][C][L], this sampler consumes " + std::to_string(ndraws));
-        if (p->inj_cap < need) {
-            if (p->inj_stage) {                      // captured graphs read the old staging buffer: drain and drop them with it
-                (void)hipDeviceSynchronize();
-                drop_graphs(p);
-                dfree(h, p->inj_stage, p->inj_cap * 4, p);
-                p->inj_stage = nullptr; p->inj_cap = 0;
-            }
-            p->inj_stage = (float*)dalloc(h, need * 4, p);
-            if (!p->inj_stage) return fail(h, "device allocation failed for injected noise");
-            p->inj_cap = need;
-        }
-        if (hipMemcpyAsync(p->inj_stage, injected_noise, need * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "injected-noise copy failed");
+        if (stage_injected(h, p, injected_noise, need, s)) return 1;
     }
     // the sigma of every denoiser evaluation of this run (host logic only), then the buffers of the per-run table -- sized
     // before any capture starts
     std::vector<float> eval_sigmas;
     if (count_sampler(desc, sigmas_host, n_sigmas, &eval_sigmas) < 0) eval_sigmas.clear();     // a schedule the sampler rejects: the real pass below reports why
     const int n_eval = (int)eval_sigmas.size();
-    p->pre_rows = n_eval;
-    if (n_eval > p->pre_cap) {
-        if (p->pre_cap) {
-            (void)hipDeviceSynchronize();
-            drop_graphs(p);
-            dfree(h, p->coef_all, (size_t)p->pre_cap * 4 * 4, p);
-            dfree(h, p->temb_all, (size_t)p->pre_cap * nd.temb * 4, p);
-            dfree(h, p->film_all, (size_t)p->pre_cap * h->film_total * 4, p);
-            p->pre_cap = 0;
-        }
-        p->coef_all = (float*)dalloc(h, (size_t)n_eval * 4 * 4, p);
-        p->temb_all = (float*)dalloc(h, (size_t)n_eval * nd.temb * 4, p);
-        p->film_all = (float*)dalloc(h, (size_t)n_eval * h->film_total * 4, p);
-        if (!p->coef_all || !p->temb_all || !p->film_all) return fail(h, "device allocation failed for the per-run sigma table");
-        p->pre_cap = n_eval;
-    }
+    if (reserve_eval_tables(h, p, n_eval)) return 1;
     // head of the loop (inside the captured graph when there is one): coefficients, sigma embeddings and FiLM projections of all
     // evaluations in three launches
-    auto sigma_table = [&](hipStream_t st) -> int {
-        if (n_eval == 0) return 0;
-        if (const char* e = launch_edm_coef_list(eval_sigmas.data(), n_eval, h->precond_for(desc->sigma_data), p->coef_all, st)) return fail(h, e);
-        if (const char* e = h->net->time_embed(p->coef_all + 1, 4, n_eval, p->temb_all, st)) return fail(h, e);
-        if (h->per_sample_film()) return 0;                    // per-sample FiLM rows (time + class embedding): projected inside each pass
-        if (const char* e = launch_film(p->temb_all, nd.temb, h->film_w, nd.temb + h->cdim, 0, h->film_b, p->film_all, n_eval,
-                                        h->film_total, st))
-            return fail(h, e);
-        return 0;
-    };
     SamplerCtx c{h, p, desc, sigmas_host, n_sigmas, s, n};
     c.precomputed = n_eval > 0;
-    float* result = nullptr;
-    if (!desc->use_graph) {
-        if (sigma_table(s)) return 1;
-        if (run_sampler(c, &result)) return 1;
-        if (hipMemcpyAsync(out, result, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "result copy failed");
-        ++h->ctr.sampler_runs; h->ctr.sampler_evals += n_eval;
-        return 0;
-    }
-    if (!h->gstream) {
-        if (hipStreamCreateWithFlags(&h->gstream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&h->ev_out, hipEventDisableTiming) != hipSuccess)
-            return fail(h, "could not create the graph stream / events");
-    }
-    hipStream_t gs = h->gstream;
-    c.s = gs;
-    // inputs staged on the caller's stream must be visible to the graph stream
-    if (hipEventRecord(h->ev_in, s) != hipSuccess || hipStreamWaitEvent(gs, h->ev_in, 0) != hipSuccess)
-        return fail(h, "stream fence (in) failed");
-    std::string key((const char*)desc, sizeof(*desc));
-    key.append((const char*)sigmas_host, (size_t)n_sigmas * 4);
-    key.push_back(injected_noise ? 'i' : 'n');
-    key.push_back(h->cond_on ? 'c' : 'u');                   // the guidance branch structure is part of the captured graph
-    key.append((const char*)&h->cond_scale, sizeof(float));
-    key.append((const char*)&h->dyn_q, sizeof(float));        // the clipping of every evaluation is part of the captured graph
-    {                                                          // ... and so are the preconditioning formulas and their parameters
-        const Precond& pc = h->precond;
-        const float pk[6] = {(float)pc.kind, pc.beta_min2, pc.two_beta_d, pc.beta_min, pc.beta_d, pc.m_minus_1};
-        key.append((const char*)pk, sizeof(pk));
-    }
-    auto it = std::find_if(p->graphs.begin(), p->graphs.end(), [&](const std::pair<std::string, hipGraphExec_t>& g) { return g.first == key; });
-    if (it != p->graphs.end() && it != p->graphs.begin()) {      // most recently used first
-        std::rotate(p->graphs.begin(), it, it + 1);
-        it = p->graphs.begin();
-    }
-    if (it == p->graphs.end()) {
-        const hipError_t be = hipStreamBeginCapture(gs, hipStreamCaptureModeRelaxed);
-        if (be != hipSuccess) return fail(h, std::string("hipStreamBeginCapture failed: ") + hipGetErrorString(be));
-        int rc = sigma_table(gs);
-        if (!rc) rc = run_sampler(c, &result);
-        if (!rc && hipMemcpyAsync(p->out_stage, result, (size_t)n * 4, hipMemcpyDeviceToDevice, gs) != hipSuccess) { rc = 1; h->err = "result copy failed (capture)"; }
-        hipGraph_t graph = nullptr;
-        const hipError_t ee = hipStreamEndCapture(gs, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return 1; }
-        if (ee != hipSuccess || !graph) return fail(h, std::string("hipStreamEndCapture failed: ") + hipGetErrorString(ee));
-        hipGraphExec_t exec = nullptr;
-        const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (ie != hipSuccess) return fail(h, std::string("hipGraphInstantiate failed: ") + hipGetErrorString(ie));
-        if (p->graphs.size() >= kMaxGraphsPerPlan) {               // every distinct (sampler, schedule, guidance) adds one: cap it
-            if (hipStreamSynchronize(gs) != hipSuccess) { (void)hipGraphExecDestroy(exec); return fail(h, "graph stream sync failed"); }
-            (void)hipGraphExecDestroy(p->graphs.back().second);
-            p->graphs.pop_back();
+    auto enqueue = [&](hipStream_t st, float** result) -> int {
+        c.s = st;
+        if (n_eval > 0) {
+            if (const char* e = launch_edm_coef_list(eval_sigmas.data(), n_eval, h->precond_for(desc->sigma_data), p->coef_all, st)) return fail(h, e);
+            if (embed_eval_tables(h, p, n_eval, st)) return 1;
         }
-        p->graphs.insert(p->graphs.begin(), std::make_pair(key, exec));
-        it = p->graphs.begin();
-        ++h->ctr.graph_captures;
+        return run_sampler(c, result);
+    };
+    std::string key;
+    if (desc->use_graph) {
+        key.assign((const char*)desc, sizeof(*desc));
+        key.append((const char*)sigmas_host, (size_t)n_sigmas * 4);
+        key.push_back(injected_noise ? 'i' : 'n');
+        append_handle_key(h, &key);
     }
-    if (hipGraphLaunch(it->second, gs) != hipSuccess) return fail(h, "hipGraphLaunch failed");
-    if (hipEventRecord(h->ev_out, gs) != hipSuccess || hipStreamWaitEvent(s, h->ev_out, 0) != hipSuccess)
-        return fail(h, "stream fence (out) failed");
-    if (hipMemcpyAsync(out, p->out_stage, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "result copy failed");
-    ++h->ctr.sampler_runs; ++h->ctr.graph_replays; h->ctr.sampler_evals += n_eval;
-    return 0;
+    return run_loop(h, p, desc->use_graph != 0, key, enqueue, out, n, n_eval, s);
+}
+
+// The table-driven loop (adf_sampler.hip: table_refusal, table_rows, run_table).  The same staging, per-run evaluation tables, capture cache and
+// counters as adf_sampler_run; the rows are uploaded as the table gives them instead of being derived from sigmas.
+int adf_sampler_run_table(adf_handle* h, const adf_table_desc* desc, const adf_table_step* steps, const float* noise, const float* injected_noise,
+                          int n_injected, float* out, int B, int L, void* stream) {
+    if (!h) return 1;
+    ADF_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const std::string why = table_refusal(desc, steps);
+    if (!why.empty()) return fail(h, "adf_sampler_run_table: " + why);
+    if (!noise) return fail(h, "adf_sampler_run_table: noise is null");
+    if (!out) return fail(h, "adf_sampler_run_table: out is null");
+    int ndraws = 0;                                           // draws of injected_noise the table reaches: 1 + the largest `draw` of a record that reads eps
+    for (int i = 0; i < desc->num_steps; ++i) {
+        if (!table_reads_eps(steps[i])) continue;
+        if (!injected_noise) return fail(h, "adf_sampler_run_table: injected_noise is null and steps[" + std::to_string(i) + "] reads eps");
+        if (steps[i].draw < 0 || steps[i].draw >= n_injected)
+            return fail(h, "adf_sampler_run_table: steps[" + std::to_string(i) + "].draw = " + std::to_string(steps[i].draw) + " is outside the " +
+                               std::to_string(n_injected) + " draws of injected_noise (n_injected)");
+        ndraws = std::max(ndraws, steps[i].draw + 1);
+    }
+    Plan* p;
+    if (get_plan(h, B, L, s, &p)) return 1;
+    const NetDims& nd = h->net->dims;
+    const long long n = (long long)B * nd.out_channels * L;
+    if (nd.in_channels != nd.out_channels) return fail(h, "adf_sampler_run_table: the handle's network needs in_channels == out_channels");
+    if (h->cdim > 0 && (!h->cond_on || h->cond_B != B))
+        return fail(h, "adf_sampler_run_table: class-conditional network: call adf_set_condition with the labels of this batch first");
+    // whatever an evaluation of the table may need (guidance, an unclipped estimate without the fused epilogue, the dynamic threshold): before any capture
+    if (ensure_cfg_buffers(h, p)) return 1;
+    if (h->dyn_q > 0.0f && !p->dyn_scale) {
+        p->dyn_scale = (float*)dalloc(h, (size_t)B * 4, p);
+        if (!p->dyn_scale) return fail(h, "adf_sampler_run_table: device allocation failed for the dynamic-threshold scales");
+    }
+    if (hipMemcpyAsync(p->noise_stage, noise, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "adf_sampler_run_table: noise copy failed");
+    if (ndraws > 0 && stage_injected(h, p, injected_noise, (size_t)ndraws * n, s)) return 1;
+    std::vector<float> rows;
+    table_rows(desc, steps, &rows);
+    const int n_eval = (int)(rows.size() / 4);
+    if (reserve_eval_tables(h, p, n_eval)) return 1;
+    auto enqueue = [&](hipStream_t st, float** result) -> int {
+        if (const char* e = launch_coef_rows(rows.data(), n_eval, p->coef_all, st)) return fail(h, e);
+        if (embed_eval_tables(h, p, n_eval, st)) return 1;
+        return run_table(h, p, desc, steps, n, st, result);
+    };
+    std::string key;
+    if (desc->use_graph) {
+        key.assign("table");                                  // no adf_sampler_desc starts with these bytes (its first field is a kind below 11)
+        key.append((const char*)desc, sizeof(*desc));
+        key.append((const char*)steps, (size_t)desc->num_steps * sizeof(*steps));
+        append_handle_key(h, &key);
+    }
+    return run_loop(h, p, desc->use_graph != 0, key, enqueue, out, n, n_eval, s);
+}
+
+int adf_sampler_table_nfe(const adf_table_desc* desc, const adf_table_step* steps) {
+    if (!table_refusal(desc, steps).empty()) return -1;
+    std::vector<float> rows;
+    table_rows(desc, steps, &rows);
+    return (int)(rows.size() / 4);
 }
 
 int adf_abi_version(void) { return ADF_ABI_VERSION; }

@@ -331,7 +331,17 @@ int forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s);
 int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out);
 int cond_rows(adf_handle* h, int B, bool null_branch, FwdIO& io);
 int ensure_cfg_buffers(adf_handle* h, Plan* p);
-int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s);
+// How one evaluation ends.  noclip: the estimate is returned as it is -- VDiffusion(for_edm=True), ReFlow: no clamp, and dynamic_threshold is never read
+// (diffusion.py:326, :388-418).  raw: the estimate IS the network output (row (c_in, t, 0, 1), ReFlow(for_edm=False)), so without guidance there is
+// nothing to combine.  dyn: rescaled by the per-sample quantile instead of clamped.
+struct EvalClip { bool noclip = false, raw = false, dyn = false; };
+inline EvalClip handle_clip(const adf_handle* h) {
+    EvalClip ec;
+    ec.noclip = h->unclipped(); ec.raw = h->raw_output(); ec.dyn = h->dyn_q > 0.0f && !ec.noclip;
+    return ec;
+}
+int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s);                        // ends as the handle is set (handle_clip)
+int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, const EvalClip& ec, hipStream_t s);
 int denoise_scalar(adf_handle* h, Plan* p, const float* x, float sigma, float sigma_data, float* out, hipStream_t s);
 // one evaluation with a sigma per sample (sigmas_dev [B] on the device): what adf_denoise enqueues, and the middle of adf_diffusion_loss
 int denoise_rows(adf_handle* h, Plan* p, const float* x, const float* sigmas_dev, float sigma_data, float* out, hipStream_t s);
@@ -386,5 +396,12 @@ int run_sampler(SamplerCtx& c, float** result);
 int count_sampler(const adf_sampler_desc* d, const float* sig, int nsig, std::vector<float>* eval_sigmas = nullptr);
 // [B][C][L] draws of the injected noise the driver reads on this schedule (0: the sampler runs without injected_noise)
 int sampler_draws(const adf_sampler_desc& d, const float* sig, int nsig);
+
+// The table-driven loop (adf_sampler_run_table, adf_sampler.hip).  table_refusal: why the table cannot run ("" when it can; host only);
+// table_rows: the (c_in, c_noise, c_skip, c_out) of its evaluations in order; run_table enqueues the loop on the rows already in Plan::coef_all.
+bool table_reads_eps(const adf_table_step& r);
+std::string table_refusal(const adf_table_desc* d, const adf_table_step* st);
+void table_rows(const adf_table_desc* d, const adf_table_step* st, std::vector<float>* rows);
+int run_table(adf_handle* h, Plan* p, const adf_table_desc* d, const adf_table_step* st, long long n, hipStream_t s, float** result);
 
 }  // namespace adf_api

@@ -120,6 +120,13 @@ const char* launch_clamp(float* x, long long n, hipStream_t st);
 const char* launch_rf_euler(float* x_next, const float* x, const float* v, float dt, long long n, hipStream_t st);
 // x_next = x + half_dt * (v + v2)
 const char* launch_rf_heun(float* x_next, const float* x, const float* v, const float* v2, float half_dt, long long n, hipStream_t st);
+// The update of the table-driven loop (adf_sampler_run_table): out = sum_{j < n} k[j] * p[j], 1 <= n <= 5 terms, optionally clamped to [-1, 1], in one
+// pass.  The caller lists only the operands it wants read (a zero coefficient is left out on the host), so a buffer that holds nothing yet is never
+// touched.  `out` may BE one of the operands (the state is updated in place); an operand that overlaps it in any other way is refused.
+struct LinTerms { const float* p[5]; float k[5]; int n; };
+const char* launch_lin(float* out, const LinTerms& t, int clampit, long long n, hipStream_t st);
+// coef[i] = rows_host[i] (four floats each: c_in, c_noise, c_skip, c_out), the values passed in the kernel arguments like launch_edm_coef_list's
+const char* launch_coef_rows(const float* rows_host, int n, float* coef, hipStream_t s);
 
 const char* launch_nlc_to_ncl_f32(const void* x, float* y, int bf16, int B, int L, int C, hipStream_t st);
 

@@ -1377,6 +1377,21 @@ const char* launch_edm_coef_list(const float* sigmas_host, int n, const Precond&
     return nullptr;
 }
 
+// Rows the host already holds (the table-driven loop): 64 rows = 256 floats per launch ride in the kernel arguments and are stored as they are.
+__global__ void coef_rows_kernel(const SigmaPack pk, int nfloats, float* __restrict__ coef) {
+    if ((int)threadIdx.x < nfloats) coef[threadIdx.x] = pk.s[threadIdx.x];
+}
+const char* launch_coef_rows(const float* rows_host, int n, float* coef, hipStream_t s) {
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        SigmaPack pk;
+        const int m = (n - i0 < 64 ? n - i0 : 64) * 4;
+        for (int i = 0; i < 256; ++i) pk.s[i] = i < m ? rows_host[(size_t)i0 * 4 + i] : 0.0f;
+        hipLaunchKernelGGL(coef_rows_kernel, dim3(1), dim3(256), 0, s, pk, m, coef + (size_t)i0 * 4);
+        if (hipGetLastError() != hipSuccess) return "coef_rows: launch failed";
+    }
+    return nullptr;
+}
+
 const char* launch_edm_coef(const float* sigmas_dev, float sigma_scalar, int nb, const Precond& pc, float* coef, hipStream_t s) {
     hipLaunchKernelGGL(edm_coef_kernel, dim3(ceil_div(nb, 64)), dim3(64), 0, s, sigmas_dev, sigma_scalar, nb, pc, coef);
     return ADF_LAUNCH_CHECK("edm_coef");
@@ -1795,6 +1810,52 @@ const char* launch_rf_heun(float* x_next, const float* x, const float* v, const 
     const long long n4 = rf_vec4(n, x_next, x, v, v2);
     hipLaunchKernelGGL(rf_heun_kernel, dim3(ew_grid(n4 ? n4 : n)), dim3(256), 0, st, x_next, x, v, v2, half_dt, n4, n);
     return ADF_LAUNCH_CHECK("rf_heun");
+}
+
+// The table-driven loop's update: out = sum_j k[j] p[j] over N operands the host chose (a zero coefficient never becomes an operand), one fused pass.
+// out may be one of the operands: element i of the result depends on element i of the operands only, and a thread reads all of its float4 (or tail
+// element) before it stores, so nothing is declared __restrict__.  n4 = n / 4 float4 elements when every pointer is 16-byte aligned, else 0; the
+// n - 4 n4 elements behind them go one by one.  The sum runs left to right with one rounding per term (fma).
+__device__ __forceinline__ float lin_clamp(float v, int clampit) { return clampit ? fminf(fmaxf(v, -1.0f), 1.0f) : v; }
+template <int N>
+__global__ void __launch_bounds__(256) lin_kernel(float* out, const LinTerms t, int clampit, long long n4, long long n) {
+    const long long t0 = (long long)blockIdx.x * 256 + threadIdx.x, stride = (long long)gridDim.x * 256;
+    for (long long i = t0; i < n4; i += stride) {
+        float4 v = reinterpret_cast<const float4*>(t.p[0])[i];
+        float4 acc = make_float4(t.k[0] * v.x, t.k[0] * v.y, t.k[0] * v.z, t.k[0] * v.w);
+#pragma unroll
+        for (int j = 1; j < N; ++j) {
+            v = reinterpret_cast<const float4*>(t.p[j])[i];
+            acc = make_float4(fmaf(t.k[j], v.x, acc.x), fmaf(t.k[j], v.y, acc.y), fmaf(t.k[j], v.z, acc.z), fmaf(t.k[j], v.w, acc.w));
+        }
+        reinterpret_cast<float4*>(out)[i] = make_float4(lin_clamp(acc.x, clampit), lin_clamp(acc.y, clampit), lin_clamp(acc.z, clampit), lin_clamp(acc.w, clampit));
+    }
+    for (long long i = 4 * n4 + t0; i < n; i += stride) {
+        float acc = t.k[0] * t.p[0][i];
+#pragma unroll
+        for (int j = 1; j < N; ++j) acc = fmaf(t.k[j], t.p[j][i], acc);
+        out[i] = lin_clamp(acc, clampit);
+    }
+}
+const char* launch_lin(float* out, const LinTerms& t, int clampit, long long n, hipStream_t st) {
+    if (!out || n < 1 || t.n < 1 || t.n > 5) return "lin: bad arguments (1 to 5 operands)";
+    uintptr_t bits = (uintptr_t)out;
+    for (int j = 0; j < t.n; ++j) {
+        const float* q = t.p[j];
+        if (!q) return "lin: null operand";
+        if (q != out && (uintptr_t)q < (uintptr_t)(out + n) && (uintptr_t)out < (uintptr_t)(q + n)) return "lin: an operand overlaps the output without being the output";
+        bits |= (uintptr_t)q;
+    }
+    const long long n4 = (bits & 15) ? 0 : n / 4;
+    const dim3 grid(ew_grid(n4 ? n4 : n)), block(256);
+    switch (t.n) {
+        case 1: hipLaunchKernelGGL(lin_kernel<1>, grid, block, 0, st, out, t, clampit, n4, n); break;
+        case 2: hipLaunchKernelGGL(lin_kernel<2>, grid, block, 0, st, out, t, clampit, n4, n); break;
+        case 3: hipLaunchKernelGGL(lin_kernel<3>, grid, block, 0, st, out, t, clampit, n4, n); break;
+        case 4: hipLaunchKernelGGL(lin_kernel<4>, grid, block, 0, st, out, t, clampit, n4, n); break;
+        default: hipLaunchKernelGGL(lin_kernel<5>, grid, block, 0, st, out, t, clampit, n4, n); break;
+    }
+    return ADF_LAUNCH_CHECK("lin");
 }
 
 // =====================================================================================================

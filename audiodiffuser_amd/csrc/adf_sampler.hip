@@ -36,11 +36,12 @@ int ensure_cfg_buffers(adf_handle* h, Plan* p) {
 // Dynamic thresholding (EluDiffusion(dynamic_threshold = q), components/utils.py:23-33): the estimate leaves the combine kernel unclipped and is
 // rescaled in place by its per-sample quantile.  The unclipped kind (ADF_PRECOND_V_EDM) keeps the combine fused in UNet2dBase's last kernel; on the other
 // nets, and under guidance, it is the raw pass + cfg_combine without the clamp.
-int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s) {
+int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s) { return denoise_io(h, p, io, out, handle_clip(h), s); }
+
+// The same with the end of the evaluation given by the caller (the table-driven loop names it per evaluation; every other caller takes the handle's).
+int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, const EvalClip& ec, hipStream_t s) {
     const bool cfg = h->cdim > 0 && h->cond_on && h->cond_scale != 1.0f;
-    const bool noclip = h->unclipped();              // VDiffusion(for_edm=True), ReFlow: no clamp, and dynamic_threshold is never read (diffusion.py:326, :388-418)
-    const bool raw = h->raw_output();                // ReFlow(for_edm=False): the estimate is the network output, so without guidance there is nothing to combine
-    const bool dyn = h->dyn_q > 0.0f && !noclip;
+    const bool noclip = ec.noclip, raw = ec.raw, dyn = ec.dyn;
     // one pass with the preconditioning in the last kernel's epilogue: clamped on every net, unclipped on UNet2dBase (u2d_conv_out_raw_kernel mode 2);
     // the raw kind is the mode 0 pass written straight into `out` on every net
     if (!cfg && !dyn && (!noclip || raw || h->net->unclipped_epilogue)) {
@@ -681,6 +682,96 @@ int sampler_draws(const adf_sampler_desc& d, const float* sig, int nsig) {
         }
         default: return 0;
     }
+}
+
+// ---- the table-driven loop (adf_sampler_run_table; the step form is in the header) --------------------------------------------------------------
+// VESampler / VPSampler (sampler_edm.py:31-227) and VSampler / VEulerSampler (sampler_vobj.py:31-194): the host resolves every branch and scalar of
+// those loops into one record per step (audiodiffuser_amd/samplers.py), so there is one driver and it knows none of them.
+bool table_reads_eps(const adf_table_step& r) { return r.a1 != 0.0f || r.b2 != 0.0f; }
+
+// Why the table cannot run, naming the argument, or "" (host only; the draws are the entry point's to check).
+std::string table_refusal(const adf_table_desc* d, const adf_table_step* st) {
+    if (!d) return "desc is null";
+    if (!st) return "steps is null";
+    if (d->num_steps <= 0) return "desc.num_steps = " + std::to_string(d->num_steps) + " must be positive";
+    if (!std::isfinite(d->x0_scale)) return "desc.x0_scale is not finite";
+    auto all_finite = [](std::initializer_list<float> v) { for (float f : v) if (!std::isfinite(f)) return false; return true; };
+    auto bad_eval = [&](const adf_table_eval& e) -> const char* {
+        if (!all_finite({e.c_in, e.c_noise, e.c_skip, e.c_out})) return " holds a non-finite row entry";
+        if (e.clip != ADF_CLIP_NONE && e.clip != ADF_CLIP_CONFIGURED && e.clip != ADF_CLIP_UNIT) return ".clip is no ADF_CLIP_* mode";
+        return nullptr;
+    };
+    for (int i = 0; i < d->num_steps; ++i) {
+        const adf_table_step& r = st[i];
+        const std::string at = "steps[" + std::to_string(i) + "]";
+        if (!all_finite({r.a0, r.a1, r.b0, r.b1, r.b2})) return at + " holds a non-finite coefficient (a0, a1, b0, b1, b2)";
+        if (const char* e = bad_eval(r.eval1)) return at + ".eval1" + e;
+        if (r.a0 == 0.0f && r.a1 == 0.0f) return at + ": a0 == a1 == 0 leaves no x_hat to evaluate";
+        const bool no_xe = r.b0 == 0.0f && r.b1 == 0.0f && r.b2 == 0.0f;
+        if (!r.second) {
+            if (no_xe) return at + ": b0 == b1 == b2 == 0 leaves no next state";
+            continue;
+        }
+        if (no_xe) return at + ".second asks for D2 without x_e (b0 == b1 == b2 == 0)";
+        if (!all_finite({r.c0, r.c1, r.c2, r.c3})) return at + " holds a non-finite coefficient (c0 .. c3)";
+        if (const char* e = bad_eval(r.eval2)) return at + ".eval2" + e;
+        if (r.c0 == 0.0f && r.c1 == 0.0f && r.c2 == 0.0f && r.c3 == 0.0f) return at + ": c0 == c1 == c2 == c3 == 0 leaves no next state";
+    }
+    return "";
+}
+
+// the rows of every evaluation of the table, in order (four floats each)
+void table_rows(const adf_table_desc* d, const adf_table_step* st, std::vector<float>* rows) {
+    rows->clear();
+    for (int i = 0; i < d->num_steps; ++i)
+        for (const adf_table_eval* e : {&st[i].eval1, st[i].second ? &st[i].eval2 : nullptr})
+            if (e) rows->insert(rows->end(), {e->c_in, e->c_noise, e->c_skip, e->c_out});
+}
+
+// Evaluation k of the run (row k of Plan::coef_all, embedded at the head of the run) on x, ending as `e.clip` says.
+static int table_eval(adf_handle* h, Plan* p, int k, const adf_table_eval& e, const float* x, float* out, hipStream_t s) {
+    FwdIO io;
+    io.x = x; io.t = p->coef_all + (size_t)k * 4 + 1; io.t_stride = 4; io.nb = 1;
+    io.coef = p->coef_all + (size_t)k * 4; io.coef_bstride = 0; io.x_noisy = x;
+    if (h->per_sample_film()) io.temb_pre = p->temb_all + (size_t)k * h->net->dims.temb;
+    else io.film_pre = p->film_all + (size_t)k * h->film_total;
+    EvalClip ec;
+    ec.noclip = e.clip == ADF_CLIP_NONE || (e.clip == ADF_CLIP_CONFIGURED && h->unclipped());
+    ec.dyn = e.clip == ADF_CLIP_CONFIGURED && h->dyn_q > 0.0f && !ec.noclip;
+    ec.raw = ec.noclip && e.c_skip == 0.0f && e.c_out == 1.0f;      // the estimate is the network output: written straight into `out`
+    return denoise_io(h, p, io, out, ec, s);
+}
+
+// One update: out = sum of the operands whose coefficient is not zero (table_refusal has seen to it that one is left).
+static int table_lin(adf_handle* h, float* out, std::initializer_list<std::pair<const float*, float>> ops, int clampit, long long n, hipStream_t s) {
+    LinTerms t;
+    memset(&t, 0, sizeof(t));
+    for (const auto& op : ops)
+        if (op.second != 0.0f) { t.p[t.n] = op.first; t.k[t.n] = op.second; ++t.n; }
+    if (const char* e = launch_lin(out, t, clampit, n, s)) return fail(h, e);
+    return 0;
+}
+
+int run_table(adf_handle* h, Plan* p, const adf_table_desc* d, const adf_table_step* st, long long n, hipStream_t s, float** result) {
+    float *X = p->sb[0], *D1 = p->sb[1], *XE = p->sb[2], *D2 = p->sb[3];
+    if (const char* e = launch_scale(X, p->noise_stage, d->x0_scale, n, s)) return fail(h, e);
+    int k = 0;
+    for (int i = 0; i < d->num_steps; ++i) {
+        const adf_table_step& r = st[i];
+        const float* eps = table_reads_eps(r) ? p->inj_stage + (size_t)r.draw * n : nullptr;
+        const int clampit = d->final_clamp && i + 1 == d->num_steps;       // the closing clamp rides in the last update
+        if (!(r.a0 == 1.0f && r.a1 == 0.0f) && table_lin(h, X, {{X, r.a0}, {eps, r.a1}}, 0, n, s)) return 1;     // X holds x_hat from here on
+        if (table_eval(h, p, k++, r.eval1, X, D1, s)) return 1;
+        if (!r.second) {
+            if (table_lin(h, X, {{X, r.b0}, {D1, r.b1}, {eps, r.b2}}, clampit, n, s)) return 1;
+            continue;
+        }
+        if (table_lin(h, XE, {{X, r.b0}, {D1, r.b1}, {eps, r.b2}}, 0, n, s)) return 1;
+        if (table_eval(h, p, k++, r.eval2, XE, D2, s)) return 1;
+        if (table_lin(h, X, {{X, r.c0}, {D1, r.c1}, {XE, r.c2}, {D2, r.c3}}, clampit, n, s)) return 1;
+    }
+    *result = X;
+    return 0;
 }
 
 }  // namespace adf_api

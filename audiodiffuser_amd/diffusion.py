@@ -291,7 +291,9 @@ class VDiffusion(Diffusion):
     """v-prediction (diffusion.py:260-365).  ``for_edm=True`` wraps the v network as an x0 denoiser over sigma = sigma_t / alpha_t, which
     is what the ``sampler_edm`` samplers drive: ``alpha_t x_in - sigma_t v`` with ``x_in = alpha_t x`` and ``alpha_t = sqrt(sigmoid(-2 ln sigma))``,
     returned unclipped (``dynamic_threshold`` is stored and never read, as in the reference).  ``for_edm=False`` returns the raw v prediction
-    at the given log-SNR for the reference's ``sampler_vobj`` samplers, which this package does not build: compatibility branch only."""
+    at the given log-SNR for the reference's ``sampler_vobj`` samplers.  Of those ``VSampler`` and ``VEulerSampler`` are built (samplers.py) and run
+    it on the device through rows of their own; ``denoise_fn`` called directly, and every other sampler given it, take the compatibility branch as before
+    (``sampler_vobj.DPMSampler`` / ``UniPCSampler`` are not built)."""
 
     _clips = False
 

@@ -194,6 +194,25 @@ class NativeHandle:
                                                 C.c_void_p(_stream_ptr(noise.device))), "adf_sampler_run")
         return out
 
+    def sampler_run_table(self, desc: "_lib.AdfTableDesc", steps, noise: torch.Tensor, injected: Optional[torch.Tensor]) -> torch.Tensor:
+        """``adf_sampler_run_table``: ``steps`` is a ctypes array of ``desc.num_steps`` ``AdfTableStep`` records (or None, which the library
+        refuses); ``injected`` the [n, *noise.shape] draws the records index."""
+        out = torch.empty_like(noise)
+        n_inj = 0
+        if injected is not None:
+            if (injected.ndim != noise.ndim + 1 or tuple(injected.shape[1:]) != tuple(noise.shape) or injected.dtype != torch.float32
+                    or injected.device != noise.device or not injected.is_contiguous()):
+                raise ValueError("injected noise must be a contiguous fp32 [n, *noise.shape] tensor on the device of `noise`")
+            n_inj = int(injected.shape[0])
+        if steps is not None and len(steps) < desc.num_steps:
+            raise ValueError(f"the table holds {len(steps)} records, desc.num_steps is {desc.num_steps}")
+        ip = C.c_void_p(injected.data_ptr()) if injected is not None else C.c_void_p(0)
+        with torch.cuda.device(noise.device):
+            self.check(self.lib.adf_sampler_run_table(self.h, C.byref(desc), steps, C.c_void_p(noise.data_ptr()), ip, n_inj,
+                                                      C.c_void_p(out.data_ptr()), noise.shape[0], self._length(noise),
+                                                      C.c_void_p(_stream_ptr(noise.device))), "adf_sampler_run_table")
+        return out
+
     def counters(self) -> Dict[str, int]:
         """What the device loop has done so far (``adf_get_counters``): sampler runs, evaluations, graph captures / replays."""
         c = _lib.AdfRunCounters()

@@ -8,11 +8,15 @@ loop runs inside ``libadf_hip.so`` (one ``adf_sampler_run`` call, optionally one
 branch conditions of the reference loop (``gamma > 0``, ``sigma_next != 0``, warm-up orders) depend only
 on the sigma schedule, so they are resolved on the host before anything is enqueued.  For any other
 callable the same recurrences are expressed with tensor ops around ``fn`` (interface compatibility).
+
+``VESampler`` / ``VPSampler`` (sampler_edm.py:31-227) and ``VSampler`` / ``VEulerSampler`` (sampler_vobj.py:31-194) go one step further: the host
+resolves a run into a table with one record per step -- coefficients of a few whole-state linear combinations and the rows of the step's one or two
+denoiser evaluations -- and one generic device loop runs it (``adf_sampler_run_table``; ``_TableSampler`` below).
 """
 from __future__ import annotations
 
 import os
-from math import sqrt
+from math import atan, exp, sqrt
 from typing import Callable, Optional, Tuple
 
 import torch
@@ -20,7 +24,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import _lib
-from .diffusion import Diffusion, EluDiffusion, conditioning_refusal
+from .diffusion import Diffusion, EluDiffusion, VDiffusion, conditioning_refusal
 from .net import HipNet, UNet1dBase
 
 
@@ -115,6 +119,393 @@ class _Sampler(nn.Module):
         plan = self._draw_plan(sigmas)
         inj = _draws(x, plan[0], injected_noise, plan[1]) if plan is not None else None
         return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, inj).to(noise.dtype)
+
+
+class _TableSampler(nn.Module):
+    """What the four table-driven samplers share (``VESampler``, ``VPSampler``, ``VSampler``, ``VEulerSampler``): every branch and scalar of their
+    reference loops depends on the schedule and the constructor arguments only, so the host resolves a run into one record per step
+    (``adf_table_step``, include/audiodiffuser_amd.h) and the device runs the table (``adf_sampler_run_table``).  A sampler gives ``_scalars`` (the
+    reference's per-step fp32 scalars, computed with the reference's own torch fp32 op sequence on CPU tensors, so they match it bit for bit),
+    ``_table`` (those scalars combined, in double, into the records) and ``_owner`` (whose ``denoise_fn`` makes a call native)."""
+
+    @staticmethod
+    def _eval(c_in: float, c_noise: float, c_skip: float, c_out: float, clip: int) -> "_lib.AdfTableEval":
+        return _lib.AdfTableEval(c_in=c_in, c_noise=c_noise, c_skip=c_skip, c_out=c_out, clip=clip)
+
+    @staticmethod
+    def _step(eval1, a=(1.0, 0.0), b=(1.0, 0.0, 0.0), eval2=None, c=(0.0, 0.0, 0.0, 0.0), draw: int = 0) -> "_lib.AdfTableStep":
+        r = _lib.AdfTableStep(a0=a[0], a1=a[1], eval1=eval1, b0=b[0], b1=b[1], b2=b[2], second=int(eval2 is not None),
+                              c0=c[0], c1=c[1], c2=c[2], c3=c[3], draw=int(draw))
+        if eval2 is not None:
+            r.eval2 = eval2
+        return r
+
+    def _refuse(self, why: str) -> None:
+        if REQUIRE_NATIVE:
+            raise RuntimeError(f"{type(self).__name__}: ADF_REQUIRE_NATIVE is set and this call would leave the device loop ({why})")
+
+    def _run_table(self, noise: Tensor, net, owner: Diffusion, kwargs: dict, steps: list, x0_scale: float, final_clamp: bool,
+                   n_draws: int, injected_noise: Optional[Tensor], configure: bool) -> Tensor:
+        """One ``adf_sampler_run_table`` call.  The order is the other samplers': the condition is set before the run, and the draws advance the
+        global generator after everything that can refuse."""
+        x = _prep(noise)
+        hd = net.native(x.device)
+        if configure:
+            owner._configure(hd)
+        if net.cfg.class_cond:
+            hd.set_condition(kwargs["classes"], x.device, null_labels=False, cond_scale=float(self.cond_scale))
+        inj = _draws(x, n_draws, injected_noise, True) if n_draws > 0 else None
+        desc = _lib.AdfTableDesc(num_steps=len(steps), x0_scale=x0_scale, final_clamp=int(final_clamp), use_graph=int(self.use_graph))
+        return hd.sampler_run_table(desc, (_lib.AdfTableStep * len(steps))(*steps), x, inj).to(noise.dtype)
+
+
+class _ChurnTableSampler(_TableSampler):
+    """The loop ``VESampler`` and ``VPSampler`` share (sampler_edm.py:55-123, :168-227; EDM algorithm 2 in the time variable of each): churn to
+    ``t_hat``, an Euler step to ``t_next`` and, wherever ``t_next != 0``, the Heun correction.  A subclass gives the reference's ``t_to_sigma`` /
+    ``sigma_to_t`` / ``t_to_sigma_deriv`` (and, VP, ``scale`` / ``scale_deriv``) and the three scalar groups that differ between the two."""
+
+    _final_clamp = True
+    _window = ("s_tmin", "s_tmax")      # the constructor's names of the churn window
+
+    def _x_hat(self, t: Tensor, t_hat: Tensor, nc: Tensor):
+        """(coefficient of x, coefficient of randn) of ``x_hat``, fp32, in the reference's order of operations."""
+        raise NotImplementedError
+
+    def _slope(self, t: Tensor):
+        """(coefficient of x, coefficient of the denoised estimate) of ``d`` at time ``t`` and the factor the state is divided by before ``fn``."""
+        raise NotImplementedError
+
+    def _x0(self, sig: Tensor, ts: Tensor) -> Tensor:
+        raise NotImplementedError
+
+    def _scalars(self, sigmas: Tensor) -> list:
+        """The fp32 scalars of every step as Python floats (each exactly an fp32 value), computed as the reference computes them: the same torch
+        ops in the same order on 0-dim / 1-D fp32 CPU tensors.  ``t_hat = sigma_to_t(t_to_sigma(t) + gamma t_to_sigma(t))`` round-trips through
+        fp32 also where ``gamma = 0``, so the noise coefficient ``a1`` of such a step is rounding-sized and, in general, not zero -- the reference
+        adds that much noise, and so does the table."""
+        sig = sigmas.detach().to("cpu", torch.float32)
+        ts = self.sigma_to_t(sig)
+        ts = torch.cat([ts, torch.zeros_like(ts[:1])])
+        lo, hi = (getattr(self, k) for k in self._window)
+        gammas = torch.where((sig >= lo) & (sig <= hi), min(self.s_churn / self.num_steps, sqrt(2) - 1), 0.0)
+        out = []
+        for i in range(self.num_steps):
+            t, t_next, gamma = ts[i], ts[i + 1], gammas[i]
+            t_hat = self.sigma_to_t(self.t_to_sigma(t) + gamma * self.t_to_sigma(t))
+            nc = (self.t_to_sigma(t_hat) ** 2 - self.t_to_sigma(t) ** 2).clip(min=0).sqrt()
+            a0, a1 = self._x_hat(t, t_hat, nc)
+            kx, kd, div = self._slope(t_hat)
+            h = t_next - t_hat
+            rec = dict(gamma=gamma, t_hat=t_hat, a0=a0, a1=a1, sigma1=self.t_to_sigma(t_hat), kx1=kx, kd1=kd, div1=div, h=h,
+                       second=bool(t_next != 0) and bool(self.use_heun))
+            if rec["second"]:
+                t_prime = t_hat + h
+                kx2, kd2, div2 = self._slope(t_prime)
+                rec.update(sigma2=self.t_to_sigma(t_prime), kx2=kx2, kd2=kd2, div2=div2)
+            out.append({k: (v if isinstance(v, bool) else float(v)) for k, v in rec.items()})
+        out[0]["x0_scale"] = float(self._x0(sig, ts))
+        return out
+
+    def _table(self, sigmas: Tensor, owner: Diffusion):
+        """(records, x0_scale, final_clamp, draws).  The rows come from ``owner.get_scale_weights`` at the fp32 sigmas the reference hands ``fn``;
+        ``fn(x / scale)`` is folded into the row (``c_in / scale``, ``c_skip / scale``), so there is no extra pass."""
+        sc = self._scalars(sigmas)
+        ev_sig = torch.tensor([v for r in sc for v in ([r["sigma1"], r["sigma2"]] if r["second"] else [r["sigma1"]])], dtype=torch.float32)
+        cols = [[float(x) for x in (v.reshape(-1) if isinstance(v, Tensor) else torch.full((len(ev_sig),), float(v)))]
+                for v in owner.get_scale_weights(ev_sig, 1)]                  # (c_skip, c_out, c_in, c_noise); VE / VP give Python ints for some
+        clip = _lib.CLIP_CONFIGURED if owner._clips else _lib.CLIP_NONE
+        k, steps = 0, []
+
+        def ev(div):
+            nonlocal k
+            c_skip, c_out, c_in, c_noise = (col[k] for col in cols)
+            k += 1
+            return self._eval(c_in / div, c_noise, c_skip / div, c_out, clip)
+
+        for i, r in enumerate(sc):
+            h = r["h"]
+            e1 = ev(r["div1"])
+            if not r["second"]:
+                steps.append(self._step(e1, a=(r["a0"], r["a1"]), b=(1.0 + h * r["kx1"], -h * r["kd1"], 0.0), draw=i))
+                continue
+            steps.append(self._step(e1, a=(r["a0"], r["a1"]), b=(1.0 + h * r["kx1"], -h * r["kd1"], 0.0), eval2=ev(r["div2"]),
+                                    c=(1.0 + 0.5 * h * r["kx1"], -0.5 * h * r["kd1"], 0.5 * h * r["kx2"], -0.5 * h * r["kd2"]), draw=i))
+        return steps, sc[0]["x0_scale"], self._final_clamp, self.num_steps       # one randn_like per step, always (sampler_edm.py:63, :176)
+
+    def _owner(self, fn: Callable, net, kwargs: dict, noise: Tensor) -> Optional[Diffusion]:
+        owner = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
+        if owner is not None and not hasattr(owner, "get_scale_weights"):
+            self._refuse(f"{type(owner).__name__} has no get_scale_weights to take the rows from")
+            return None
+        return owner
+
+    @torch.no_grad()
+    def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, injected_noise: Optional[Tensor] = None, **kwargs) -> Tensor:
+        owner = self._owner(fn, net, kwargs, noise)
+        if owner is not None:
+            steps, x0, clamp, n_draws = self._table(sigmas, owner)
+            return self._run_table(noise, net, owner, kwargs, steps, x0, clamp, n_draws, injected_noise, configure=True)
+        return self._compat(noise, fn, net, sigmas, injected_noise, kwargs)
+
+
+class VESampler(_ChurnTableSampler):
+    """EDM's variance-exploding sampler (sampler_edm.py:31-123): time ``t = sigma^2``, one ``randn_like`` per step, Heun wherever ``t_next != 0``,
+    final clamp.  ``injected_noise`` ([num_steps, B, C, L]) replaces the draws."""
+
+    def __init__(self, s_tmin: float = 0, s_tmax: float = float("inf"), s_churn: float = 200, s_noise: float = 1, num_steps: int = 200,
+                 cond_scale: float = 1.0, use_heun: bool = True, use_graph: bool = True):
+        super().__init__()
+        self.s_tmin, self.s_tmax, self.s_churn, self.s_noise = s_tmin, s_tmax, s_churn, s_noise
+        self.num_steps, self.cond_scale, self.use_heun, self.use_graph = num_steps, cond_scale, use_heun, use_graph
+
+    def t_to_sigma(self, t: Tensor) -> Tensor:
+        return t.sqrt()
+
+    def t_to_sigma_deriv(self, t: Tensor) -> Tensor:
+        return 0.5 / t.sqrt()
+
+    def sigma_to_t(self, sigma: Tensor) -> Tensor:
+        return sigma ** 2
+
+    def _x_hat(self, t, t_hat, nc):
+        return 1.0, nc * self.s_noise                                                     # :63
+
+    def _slope(self, t):
+        r = self.t_to_sigma_deriv(t) / self.t_to_sigma(t)                                 # :72, :85: the same quotient in front of x and of the estimate
+        return r, r, 1.0
+
+    def _x0(self, sig, ts):
+        return sig[0]                                                                     # :115
+
+    def _compat(self, noise, fn, net, sigmas, injected_noise, kwargs):
+        """sampler_edm.py:55-123 as written."""
+        ts = self.sigma_to_t(sigmas)
+        ts = torch.cat([ts, torch.zeros_like(ts[:1])])
+        gammas = torch.where((sigmas >= self.s_tmin) & (sigmas <= self.s_tmax), min(self.s_churn / self.num_steps, sqrt(2) - 1), 0.0)
+        call = lambda x_, t_: fn(x_, net=net, sigma=self.t_to_sigma(t_), inference=True, cond_scale=self.cond_scale, **kwargs)
+        x = noise * sigmas[0]
+        for i in range(self.num_steps):
+            t, t_next, gamma = ts[i], ts[i + 1], gammas[i]
+            eps = injected_noise[i] if injected_noise is not None else torch.randn_like(x)
+            t_hat = self.sigma_to_t(self.t_to_sigma(t) + gamma * self.t_to_sigma(t))
+            x_hat = x + (self.t_to_sigma(t_hat) ** 2 - self.t_to_sigma(t) ** 2).clip(min=0).sqrt() * self.s_noise * eps
+            r = self.t_to_sigma_deriv(t_hat) / self.t_to_sigma(t_hat)
+            d = r * x_hat - r * call(x_hat, t_hat)
+            h = t_next - t_hat
+            x = x_hat + h * d
+            if t_next != 0 and self.use_heun:
+                t_prime = t_hat + h
+                r2 = self.t_to_sigma_deriv(t_prime) / self.t_to_sigma(t_prime)
+                d_prime = r2 * x - r2 * call(x, t_prime)
+                x = x_hat + 1 / 2 * h * (d + d_prime)
+        return x.clamp(-1.0, 1.0)
+
+
+class VPSampler(_ChurnTableSampler):
+    """EDM's variance-preserving sampler (sampler_edm.py:125-227): the state is ``scale(t) * (x0 + sigma(t) noise)``, ``fn`` sees ``x / scale(t)``;
+    one ``randn_like`` per step, Heun wherever ``t_next != 0``; the result is returned UNCLAMPED, as in the reference.  ``injected_noise``
+    ([num_steps, B, C, L]) replaces the draws."""
+
+    _final_clamp = False
+    _window = ("s_min", "s_max")
+
+    def __init__(self, beta_d: float = 19.9, beta_min: float = 0.1, s_churn: float = 200.0, s_noise: float = 1.0, s_min: float = 0.0,
+                 s_max: float = float("inf"), num_steps: int = 200, cond_scale: float = 1.0, use_heun: bool = True, use_graph: bool = True):
+        super().__init__()
+        self.beta_d, self.beta_min, self.s_noise, self.s_churn, self.s_min, self.s_max = beta_d, beta_min, s_noise, s_churn, s_min, s_max
+        self.num_steps, self.cond_scale, self.use_heun, self.use_graph = num_steps, cond_scale, use_heun, use_graph
+
+    def t_to_sigma(self, t: Tensor) -> Tensor:
+        return ((0.5 * self.beta_d * (t ** 2) + self.beta_min * t).exp() - 1) ** 0.5
+
+    def sigma_to_t(self, sigma: Tensor) -> Tensor:
+        return ((self.beta_min ** 2 + 2 * self.beta_d * (sigma ** 2 + 1).log()).sqrt() - self.beta_min) / self.beta_d
+
+    def t_to_sigma_deriv(self, t: Tensor) -> Tensor:
+        return 0.5 * (self.beta_min + self.beta_d * t) * (self.t_to_sigma(t) + 1 / self.t_to_sigma(t))
+
+    def scale(self, t: Tensor) -> Tensor:
+        return 1 / (1 + self.t_to_sigma(t) ** 2).sqrt()
+
+    def scale_deriv(self, t: Tensor) -> Tensor:
+        return -self.t_to_sigma(t) * self.t_to_sigma_deriv(t) * (self.scale(t) ** 3)
+
+    def _x_hat(self, t, t_hat, nc):
+        return self.scale(t_hat) / self.scale(t), nc * self.scale(t_hat) * self.s_noise                                  # :176
+
+    def _slope(self, t):
+        return (self.t_to_sigma_deriv(t) / self.t_to_sigma(t) + self.scale_deriv(t) / self.scale(t),                     # :184, :196
+                self.t_to_sigma_deriv(t) * self.scale(t) / self.t_to_sigma(t), self.scale(t))
+
+    def _x0(self, sig, ts):
+        return sig[0].double() * self.scale(ts[0]).double()                                                               # :218
+
+    def _compat(self, noise, fn, net, sigmas, injected_noise, kwargs):
+        """sampler_edm.py:168-227 as written."""
+        ts = self.sigma_to_t(sigmas)
+        ts = torch.cat([ts, torch.zeros_like(ts[:1])])
+        gammas = torch.where((sigmas >= self.s_min) & (sigmas <= self.s_max), min(self.s_churn / self.num_steps, sqrt(2) - 1), 0.0)
+        call = lambda x_, t_: fn(x_ / self.scale(t_), net=net, sigma=self.t_to_sigma(t_), inference=True, cond_scale=self.cond_scale, **kwargs)
+        slope = lambda x_, t_: ((self.t_to_sigma_deriv(t_) / self.t_to_sigma(t_) + self.scale_deriv(t_) / self.scale(t_)) * x_
+                                - self.t_to_sigma_deriv(t_) * self.scale(t_) / self.t_to_sigma(t_) * call(x_, t_))
+        x = noise * sigmas[0] * self.scale(ts[0])
+        for i in range(self.num_steps):
+            t, t_next, gamma = ts[i], ts[i + 1], gammas[i]
+            eps = injected_noise[i] if injected_noise is not None else torch.randn_like(x)
+            t_hat = self.sigma_to_t(self.t_to_sigma(t) + gamma * self.t_to_sigma(t))
+            x_hat = (self.scale(t_hat) / self.scale(t) * x
+                     + (self.t_to_sigma(t_hat) ** 2 - self.t_to_sigma(t) ** 2).clip(min=0).sqrt() * self.scale(t_hat) * self.s_noise * eps)
+            d = slope(x_hat, t_hat)
+            h = t_next - t_hat
+            x = x_hat + h * d
+            if t_next != 0 and self.use_heun:
+                x = x_hat + 1 / 2 * h * (d + slope(x, t_hat + h))
+        return x
+
+
+class _VObjTableSampler(_TableSampler):
+    """What ``VSampler`` and ``VEulerSampler`` share (sampler_vobj.py:31-194): ``sigmas`` are times in [0, 1], mapped by the SAMPLER's shifted cosine
+    schedule to the log-SNR the v network is evaluated at; ``fn`` is the ``denoise_fn`` of a ``VDiffusion(for_edm=False)``, which returns the
+    raw v prediction.  That class keeps ``_precond() is None`` (no other sampler may take it), so these two have their own pair check."""
+
+    def shifted_cosine_transform(self, t: Tensor) -> Tensor:
+        t_min = atan(exp(-0.5 * self.logsnr_max))
+        t_max = atan(exp(-0.5 * self.logsnr_min))
+        return -2 * (torch.tan(t_min + t * (t_max - t_min)).log()) + 2 * self.shift
+
+    def _scalars(self, sigmas: Tensor) -> list:
+        """Per step the reference's fp32 scalars (Python floats, each exactly an fp32 value), by its own op sequence on 0-dim CPU tensors."""
+        ts = sigmas.detach().to("cpu", torch.float32)
+        ts = torch.cat([ts, torch.zeros_like(ts[:1])])
+        out = []
+        for i in range(self.num_steps):
+            t, t_next = ts[i], ts[i + 1]
+            lt, ls = self.shifted_cosine_transform(t), self.shifted_cosine_transform(t_next)
+            rec = dict(logsnr_t=lt, logsnr_s=ls, alpha_t=torch.sqrt(torch.sigmoid(lt)), sigma_t=torch.sqrt(torch.sigmoid(-lt)),
+                       alpha_s=torch.sqrt(torch.sigmoid(ls)), sigma_s=torch.sqrt(torch.sigmoid(-ls)), last=bool(t_next == 0))
+            self._more_scalars(rec)
+            out.append({k: (v if isinstance(v, bool) else float(v)) for k, v in rec.items()})
+        return out
+
+    def _owner(self, fn: Callable, net, kwargs: dict, noise: Tensor) -> Optional[VDiffusion]:
+        owner = getattr(fn, "__self__", None)
+        if not (isinstance(owner, VDiffusion) and getattr(fn, "__func__", None) is Diffusion.denoise_fn):
+            why = "fn is not the denoise_fn of an audiodiffuser_amd VDiffusion"
+        elif owner.for_edm:
+            why = "VDiffusion(for_edm=True) is an x0 denoiser over sigma: it goes with the sampler_edm samplers, these two take the raw v of for_edm=False"
+        elif not isinstance(net, HipNet):
+            why = "net is not one of this package's HIP networks"
+        elif not noise.is_cuda:
+            why = "noise is not on a ROCm device"
+        else:
+            why = conditioning_refusal(net, self.cond_scale, kwargs)
+        if why is None:
+            return owner
+        self._refuse(why)
+        return None
+
+    @torch.no_grad()
+    def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, injected_noise: Optional[Tensor] = None, **kwargs) -> Tensor:
+        owner = self._owner(fn, net, kwargs, noise)
+        if owner is not None:
+            steps, n_draws = self._table(sigmas)
+            return self._run_table(noise, net, owner, kwargs, steps, 1.0, True, n_draws, injected_noise, configure=False)
+        return self._compat(noise, fn, net, sigmas, injected_noise, kwargs)
+
+
+class VSampler(_VObjTableSampler):
+    """The stochastic v-diffusion sampler of simple diffusion (sampler_vobj.py:111-194): per step one v prediction, ``x_pred = clamp(alpha_t x -
+    sigma_t v)``, the posterior mean towards the next log-SNR and, wherever ``t_next != 0``, one ``randn_like`` draw at the posterior variance;
+    final clamp.  ``injected_noise`` ([that many, B, C, L]) replaces the draws."""
+
+    def __init__(self, logsnr_min=-15, logsnr_max=15, shift=0.0, num_steps=200, cond_scale=1.0, use_graph: bool = True):
+        super().__init__()
+        self.logsnr_min, self.logsnr_max, self.shift = logsnr_min, logsnr_max, shift
+        self.num_steps, self.cond_scale, self.use_graph = num_steps, cond_scale, use_graph
+
+    def _more_scalars(self, rec: dict) -> None:
+        rec["c"] = -torch.special.expm1(rec["logsnr_t"] - rec["logsnr_s"])                     # :154
+        rec["std"] = torch.sqrt((rec["sigma_s"] ** 2) * rec["c"])                              # :156, :159
+
+    def _table(self, sigmas: Tensor):
+        """The row (1, logsnr_t, alpha_t, -sigma_t) with the unit clamp makes the evaluation's epilogue yield ``x_pred`` itself."""
+        steps, k = [], 0
+        for r in self._scalars(sigmas):
+            e = self._eval(1.0, r["logsnr_t"], r["alpha_t"], -r["sigma_t"], _lib.CLIP_UNIT)
+            b = (r["alpha_s"] * (1.0 - r["c"]) / r["alpha_t"], r["alpha_s"] * r["c"], 0.0 if r["last"] else r["std"])
+            steps.append(self._step(e, b=b, draw=k))
+            k += 0 if r["last"] else 1
+        return steps, k
+
+    def _compat(self, noise, fn, net, sigmas, injected_noise, kwargs):
+        """sampler_vobj.py:131-194 as written."""
+        ts = torch.cat([sigmas, torch.zeros_like(sigmas[:1])])
+        x, k = noise, 0
+        for i in range(self.num_steps):
+            t, t_next = ts[i], ts[i + 1]
+            lt, ls = self.shifted_cosine_transform(t), self.shifted_cosine_transform(t_next)
+            v = fn(x, net=net, sigma=lt, inference=True, cond_scale=self.cond_scale, **kwargs)
+            alpha_t, sigma_t = torch.sqrt(torch.sigmoid(lt)), torch.sqrt(torch.sigmoid(-lt))
+            alpha_s, sigma_s = torch.sqrt(torch.sigmoid(ls)), torch.sqrt(torch.sigmoid(-ls))
+            x_pred = (alpha_t * x - sigma_t * v).clamp(-1.0, 1.0)
+            c = -torch.special.expm1(lt - ls)
+            mu = alpha_s * (x * (1 - c) / alpha_t + c * x_pred)
+            if t_next != 0:
+                eps = injected_noise[k] if injected_noise is not None else torch.randn_like(mu)
+                k += 1
+                mu = mu + eps * torch.sqrt((sigma_s ** 2) * c)
+            x = mu
+        return x.clamp(-1.0, 1.0)
+
+
+class VEulerSampler(_VObjTableSampler):
+    """The deterministic sibling (sampler_vobj.py:31-109): an Euler step of the probability-flow ODE in log-SNR, with ``use_heun`` a second v
+    prediction at the next log-SNR; the step into ``t_next = 0`` returns ``alpha_t x - sigma_t v``; final clamp.  It draws nothing;
+    ``injected_noise`` is accepted for the shared signature and ignored."""
+
+    def __init__(self, logsnr_min=-15, logsnr_max=15, shift=0.5, num_steps=200, cond_scale=1.0, use_heun=False, use_graph: bool = True):
+        super().__init__()
+        self.logsnr_min, self.logsnr_max, self.shift = logsnr_min, logsnr_max, shift
+        self.num_steps, self.cond_scale, self.use_heun, self.use_graph = num_steps, cond_scale, use_heun, use_graph
+
+    def _more_scalars(self, rec: dict) -> None:
+        dl = rec["logsnr_s"] - rec["logsnr_t"]
+        rec.update(k_cur=-rec["alpha_t"] * rec["sigma_t"], k_next=-rec["alpha_s"] * rec["sigma_s"], half_dl=0.5 * dl, quarter_dl=0.25 * dl)      # :76-83
+
+    def _table(self, sigmas: Tensor):
+        """The row (1, logsnr, 0, 1) without a clip: the evaluation is the raw v."""
+        steps = []
+        for r in self._scalars(sigmas):
+            e = self._eval(1.0, r["logsnr_t"], 0.0, 1.0, _lib.CLIP_NONE)
+            if r["last"]:
+                steps.append(self._step(e, b=(r["alpha_t"], -r["sigma_t"], 0.0)))
+            elif not self.use_heun:
+                steps.append(self._step(e, b=(1.0, r["half_dl"] * r["k_cur"], 0.0)))
+            else:
+                steps.append(self._step(e, b=(1.0, r["half_dl"] * r["k_cur"], 0.0), eval2=self._eval(1.0, r["logsnr_s"], 0.0, 1.0, _lib.CLIP_NONE),
+                                        c=(1.0, r["quarter_dl"] * r["k_cur"], 0.0, r["quarter_dl"] * r["k_next"])))
+        return steps, 0
+
+    def _compat(self, noise, fn, net, sigmas, injected_noise, kwargs):
+        """sampler_vobj.py:53-109 as written."""
+        ts = torch.cat([sigmas, torch.zeros_like(sigmas[:1])])
+        x = noise
+        for i in range(self.num_steps):
+            t, t_next = ts[i], ts[i + 1]
+            lt, ls = self.shifted_cosine_transform(t), self.shifted_cosine_transform(t_next)
+            v = fn(x, net=net, sigma=lt, inference=True, cond_scale=self.cond_scale, **kwargs)
+            alpha_t, sigma_t = torch.sqrt(torch.sigmoid(lt)), torch.sqrt(torch.sigmoid(-lt))
+            alpha_s, sigma_s = torch.sqrt(torch.sigmoid(ls)), torch.sqrt(torch.sigmoid(-ls))
+            if t_next == 0.0:
+                x = alpha_t * x - sigma_t * v
+                continue
+            score = -alpha_t * sigma_t * v
+            x_next = x + 0.5 * (ls - lt) * score
+            if self.use_heun:
+                v_next = fn(x_next, net=net, sigma=ls, inference=True, cond_scale=self.cond_scale, **kwargs)
+                x_next = x + 0.25 * (ls - lt) * (-alpha_s * sigma_s * v_next + score)
+            x = x_next
+        return x.clamp(-1.0, 1.0)
 
 
 class EDMSampler(_Sampler):

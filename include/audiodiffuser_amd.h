@@ -9,6 +9,8 @@
  *   adf_sampler_run                <- EDMSampler.forward / EDMAlphaSampler.forward / DPMSampler.forward (multistep) /
  *                                     DPM2Sampler.forward (src/models/components/sampler_edm.py:371-397, :284-300,
  *                                     :710-768, :470-493), ADPM2Sampler.forward (stochastic_sampler_edm.py:85-100), UniPCSampler.forward (:996-1053)
+ *   adf_sampler_run_table          <- VESampler.forward / VPSampler.forward (sampler_edm.py:99-123, :201-227), VSampler.forward / VEulerSampler.forward
+ *                                     (src/models/components/sampler_vobj.py:176-194, :92-109): one generic loop over a host table of per-step records
  *   the call site all of them sit behind: src/models/diffunet_complex_module.py:86-89
  *   adf_adm_create                 <- UNetModel.__init__ (src/models/backbones/unet2d_oai.py:410-601); adf_net_forward on that handle
  *                                     <- UNetModel.forward (:603-634)
@@ -57,7 +59,10 @@ extern "C" {
  *    Also without a bump (new values of existing int arguments / fields; no struct grows and no argument list changes, and a library of version 7 without
  *    them refuses both with its "unknown kind" errors): ADF_PRECOND_RF / ADF_PRECOND_RF_EDM (ReFlow) and ADF_SAMPLER_RF_EULER (ReflowEulerSampler).
  *    Added without a bump (new symbols only): adf_diffusion_loss with the three ADF_LOSS_* kinds, and adf_loss_calls -- a counter of its own,
- *    because adf_run_counters must not grow within a version. */
+ *    because adf_run_counters must not grow within a version.
+ *    Added without a bump (new symbols only): adf_sampler_run_table and adf_sampler_table_nfe with their own adf_table_desc / adf_table_step /
+ *    adf_table_eval and the three ADF_CLIP_* modes (VESampler, VPSampler, VSampler, VEulerSampler).  No ADF_SAMPLER_* or ADF_PRECOND_* kind is added:
+ *    adf_sampler_desc, its kinds and adf_set_preconditioning are as they were. */
 #define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
@@ -263,6 +268,58 @@ int64_t adf_loss_calls(const adf_handle* h);   /* successful adf_diffusion_loss 
 int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* sigmas_host, int n_sigmas,
                     const float* noise, const float* injected_noise, int n_injected, float* out, int B, int L, void* stream);
 int adf_sampler_nfe(const adf_sampler_desc* desc, const float* sigmas_host, int n_sigmas);
+
+/* The table-driven loop: a sampler whose every branch and scalar depends on the schedule and the constructor arguments only, handed over as one
+ * host record per step.  What runs VESampler / VPSampler (src/models/components/sampler_edm.py:31-227) and VSampler / VEulerSampler
+ * (sampler_vobj.py:31-194); audiodiffuser_amd/samplers.py builds their tables.  With x the fp32 state, eps the record's draw and D a denoiser
+ * evaluation out = clip(c_skip x_in + c_out net(c_in x_in, c_noise)), step i is
+ *     x_hat = a0 x + a1 eps
+ *     D1    = denoise(eval1, x_hat)
+ *     x_e   = b0 x_hat + b1 D1 + b2 eps                     (second == 0: x = x_e, the step ends here)
+ *     D2    = denoise(eval2, x_e)
+ *     x     = c0 x_hat + c1 D1 + c2 x_e + c3 D2
+ * and the run is x = x0_scale * noise, the steps, then clamp(-1, 1) where final_clamp != 0.  Every linear combination is one fused pass over the state,
+ * in place; an operand whose coefficient is zero is not read (so a record with a1 == b2 == 0 needs no draw, and a0 == 1, a1 == 0 launches nothing).
+ * The rows are taken as given -- the handle's preconditioning kind is not consulted -- and land in the per-run table adf_debug_coef_rows returns; the
+ * time embedding and the FiLM projections of all evaluations are computed once at the head of the run, as in adf_sampler_run.  `clip` of an evaluation:
+ *     ADF_CLIP_NONE        the estimate as it is
+ *     ADF_CLIP_CONFIGURED  what the handle is set to: clamp(-1, 1), the dynamic threshold of adf_set_dynamic_threshold, or nothing under an unclipped
+ *                          preconditioning kind (ADF_PRECOND_V_EDM, _RF, _RF_EDM)
+ *     ADF_CLIP_UNIT        clamp(-1, 1) whatever the handle is set to
+ * Class labels and guidance (adf_set_condition) apply as in adf_sampler_run: cond_scale != 1 is two passes per evaluation.  injected_noise:
+ * [n_injected][B][C][L]; a record that reads eps reads draw number `draw` of it.  use_graph: the whole run is captured once as a single chain and
+ * replayed; the cache key holds the descriptor and table bytes and the handle's condition, clipping and preconditioning state.  adf_run_counters moves
+ * as for adf_sampler_run (sampler_runs + 1, sampler_evals + the table's NFE, graph_replays + 1 when replayed).
+ * Refused before anything is launched, with a message that starts with "adf_sampler_run_table: " and names the argument: a null desc, steps, noise
+ * or out; num_steps <= 0; a non-finite x0_scale, coefficient or row entry; an unknown clip; second != 0 with b0 == b1 == b2 == 0 (D2 without x_e);
+ * a record that reads eps with injected_noise null or draw outside [0, n_injected).
+ * adf_sampler_table_nfe: host only; the evaluations of the table (one per record, two where second != 0), or -1 for a table the run would refuse
+ * for what the table itself holds (the draws are not known here). */
+#define ADF_CLIP_NONE 0
+#define ADF_CLIP_CONFIGURED 1
+#define ADF_CLIP_UNIT 2
+typedef struct adf_table_eval {
+    float c_in, c_noise, c_skip, c_out;
+    int32_t clip;                 /* ADF_CLIP_* */
+} adf_table_eval;
+typedef struct adf_table_step {
+    float a0, a1;
+    adf_table_eval eval1;
+    float b0, b1, b2;
+    int32_t second;               /* != 0: the step has the second evaluation and the c0..c3 update */
+    adf_table_eval eval2;         /* read where second != 0 */
+    float c0, c1, c2, c3;         /* read where second != 0 */
+    int32_t draw;                 /* index of the [B][C][L] draw this record's eps is; read where a1 != 0 or b2 != 0 */
+} adf_table_step;
+typedef struct adf_table_desc {
+    int32_t num_steps;            /* records behind `steps` */
+    float x0_scale;               /* x = x0_scale * noise */
+    int32_t final_clamp;
+    int32_t use_graph;
+} adf_table_desc;
+int adf_sampler_run_table(adf_handle* h, const adf_table_desc* desc, const adf_table_step* steps, const float* noise, const float* injected_noise,
+                          int n_injected, float* out, int B, int L, void* stream);
+int adf_sampler_table_nfe(const adf_table_desc* desc, const adf_table_step* steps);
 
 /* Parity-test support: copy an internal activation of the LAST adf_net_forward/adf_denoise call, converted to
  * fp32 [B][C][L].  Names follow oracle/unet1d.py taps ("to_in", "down0.conv", "down0.block1", "mid.attn", ...). */
