@@ -4,7 +4,7 @@ Plugin surface (hydra ``_target_`` s): ``audiodiffuser_amd.UNet1dBase`` / ``audi
 ``audiodiffuser_amd.UNet2dBase`` (model.net),
 ``audiodiffuser_amd.EluDiffusion`` / ``VEDiffusion`` / ``VPDiffusion`` / ``VDiffusion`` / ``ReFlow`` (model.diffusion), ``audiodiffuser_amd.EDMSampler`` /
 ``EDMAlphaSampler`` / ``DPMSampler`` / ``DPM2Sampler`` / ``DPM2MSampler`` / ``ADPM2Sampler`` / ``ADPMPP2SSampler`` / ``LMSSampler`` / ``UniPCSampler`` /
-``ReflowEulerSampler`` / ``VESampler`` / ``VPSampler`` / ``VSampler`` / ``VEulerSampler`` (model.sampler), ``audiodiffuser_amd.KarrasSchedule`` / ``VESchedule`` / ``VPSchedule`` / ``VSchedule`` / ``LinearSchedule`` /
+``ReflowEulerSampler`` / ``VESampler`` / ``VPSampler`` / ``VSampler`` / ``VEulerSampler`` / ``VDPMSampler`` / ``VUniPCSampler`` (model.sampler), ``audiodiffuser_amd.KarrasSchedule`` / ``VESchedule`` / ``VPSchedule`` / ``VSchedule`` / ``LinearSchedule`` /
 ``GeometricSchedule`` / ``RFEDMSchedule`` (model.noise_scheduler), ``audiodiffuser_amd.LogNormalDistribution`` / ``UniformDistribution`` /
 ``LogUniformDistribution`` / ``LogitDistribution`` (model.noise_distribution), ``audiodiffuser_amd.SpecToWave`` (the sampled complex spectrogram to audio: spec_back + inverse STFT),
 ``audiodiffuser_amd.WaveToSpec`` (a waveform to that spectrogram: STFT + spec_fwd).
@@ -21,5 +21,5 @@ from .unet2d import UNet2dBase  # noqa: F401
 from .unet2d_config import UNet2dConfig  # noqa: F401
 from .diffusion import EluDiffusion, VEDiffusion, VPDiffusion, VDiffusion, ReFlow  # noqa: F401
 from .samplers import EDMSampler, EDMAlphaSampler, DPMSampler, DPM2Sampler, DPM2MSampler, ADPM2Sampler, ADPMPP2SSampler, LMSSampler, UniPCSampler  # noqa: F401
-from .samplers import ReflowEulerSampler, VESampler, VPSampler, VSampler, VEulerSampler  # noqa: F401
+from .samplers import ReflowEulerSampler, VESampler, VPSampler, VSampler, VEulerSampler, VDPMSampler, VUniPCSampler  # noqa: F401
 from .spectral import SpecToWave, WaveToSpec  # noqa: F401

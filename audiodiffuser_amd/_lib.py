@@ -80,6 +80,20 @@ class AdfTableDesc(C.Structure):
     _fields_ = [("num_steps", C.c_int32), ("x0_scale", C.c_float), ("final_clamp", C.c_int32), ("use_graph", C.c_int32)]
 
 
+PROG_EVAL, PROG_LIN, PROG_SLOTS, PROG_TERMS = 0, 1, 8, 5      # ADF_PROG_* (adf_prog_op)
+
+
+class AdfProgOp(C.Structure):
+    """``adf_prog_op``: one op of the program-driven loop (``adf_sampler_run_program``)."""
+    _fields_ = [("kind", C.c_int32), ("dst", C.c_int32), ("src", C.c_int32), ("eval", AdfTableEval), ("n_terms", C.c_int32),
+                ("slot", C.c_int32 * PROG_TERMS), ("coef", C.c_float * PROG_TERMS), ("clamp", C.c_int32)]
+
+
+class AdfProgDesc(C.Structure):
+    """``adf_prog_desc``."""
+    _fields_ = [("num_ops", C.c_int32), ("result_slot", C.c_int32), ("x0_scale", C.c_float), ("use_graph", C.c_int32)]
+
+
 class AdfWaveNetConfig(C.Structure):
     """``adf_wavenet_config`` of include/audiodiffuser_amd.h."""
     _fields_ = [("residual_channels", C.c_int32), ("residual_layers", C.c_int32), ("dilation_cycle", C.c_int32),
@@ -164,6 +178,8 @@ EXPORTS = {
     "adf_sampler_run_table": (C.c_int, [C.c_void_p, C.POINTER(AdfTableDesc), C.POINTER(AdfTableStep), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                         C.c_int, C.c_int, C.c_void_p]),
     "adf_sampler_table_nfe": (C.c_int, [C.POINTER(AdfTableDesc), C.POINTER(AdfTableStep)]),
+    "adf_sampler_run_program": (C.c_int, [C.c_void_p, C.POINTER(AdfProgDesc), C.POINTER(AdfProgOp), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "adf_sampler_program_nfe": (C.c_int, [C.POINTER(AdfProgDesc), C.POINTER(AdfProgOp)]),
     "adf_debug_tap_shape": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "adf_debug_tap_copy": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p]),
     "adf_debug_tap_stats": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),

@@ -556,6 +556,56 @@ int adf_sampler_table_nfe(const adf_table_desc* desc, const adf_table_step* step
     return (int)(rows.size() / 4);
 }
 
+// The program-driven loop (adf_sampler.hip: program_refusal, program_rows, run_program): adf_sampler_run_table's staging, per-run evaluation tables,
+// capture cache and counters around a straight-line program over the plan's state buffers.  It reads no draws.
+int adf_sampler_run_program(adf_handle* h, const adf_prog_desc* desc, const adf_prog_op* ops, const float* noise, float* out, int B, int L, void* stream) {
+    if (!h) return 1;
+    ADF_ON_DEVICE(h);
+    hipStream_t s = (hipStream_t)stream;
+    const std::string why = program_refusal(desc, ops);
+    if (!why.empty()) return fail(h, "adf_sampler_run_program: " + why);
+    if (!noise) return fail(h, "adf_sampler_run_program: noise is null");
+    if (!out) return fail(h, "adf_sampler_run_program: out is null");
+    Plan* p;
+    if (get_plan(h, B, L, s, &p)) return 1;
+    const NetDims& nd = h->net->dims;
+    const long long n = (long long)B * nd.out_channels * L;
+    if (nd.in_channels != nd.out_channels) return fail(h, "adf_sampler_run_program: the handle's network needs in_channels == out_channels");
+    if (h->cdim > 0 && (!h->cond_on || h->cond_B != B))
+        return fail(h, "adf_sampler_run_program: class-conditional network: call adf_set_condition with the labels of this batch first");
+    // whatever an evaluation of the program may need (guidance, an unclipped estimate without the fused epilogue, the dynamic threshold): before any capture
+    if (ensure_cfg_buffers(h, p)) return 1;
+    if (h->dyn_q > 0.0f && !p->dyn_scale) {
+        p->dyn_scale = (float*)dalloc(h, (size_t)B * 4, p);
+        if (!p->dyn_scale) return fail(h, "adf_sampler_run_program: device allocation failed for the dynamic-threshold scales");
+    }
+    if (hipMemcpyAsync(p->noise_stage, noise, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "adf_sampler_run_program: noise copy failed");
+    std::vector<float> rows;
+    program_rows(desc, ops, &rows);
+    const int n_eval = (int)(rows.size() / 4);
+    if (reserve_eval_tables(h, p, n_eval)) return 1;
+    auto enqueue = [&](hipStream_t st, float** result) -> int {
+        if (const char* e = launch_coef_rows(rows.data(), n_eval, p->coef_all, st)) return fail(h, e);
+        if (embed_eval_tables(h, p, n_eval, st)) return 1;
+        return run_program(h, p, desc, ops, n, st, result);
+    };
+    std::string key;
+    if (desc->use_graph) {
+        key.assign("program");                                // no other key starts with these bytes ("table", or a sampler kind below 11)
+        key.append((const char*)desc, sizeof(*desc));
+        key.append((const char*)ops, (size_t)desc->num_ops * sizeof(*ops));
+        append_handle_key(h, &key);
+    }
+    return run_loop(h, p, desc->use_graph != 0, key, enqueue, out, n, n_eval, s);
+}
+
+int adf_sampler_program_nfe(const adf_prog_desc* desc, const adf_prog_op* ops) {
+    if (!program_refusal(desc, ops).empty()) return -1;
+    std::vector<float> rows;
+    program_rows(desc, ops, &rows);
+    return (int)(rows.size() / 4);
+}
+
 int adf_abi_version(void) { return ADF_ABI_VERSION; }
 
 int adf_get_counters(const adf_handle* h, adf_run_counters* out) {

@@ -403,5 +403,9 @@ bool table_reads_eps(const adf_table_step& r);
 std::string table_refusal(const adf_table_desc* d, const adf_table_step* st);
 void table_rows(const adf_table_desc* d, const adf_table_step* st, std::vector<float>* rows);
 int run_table(adf_handle* h, Plan* p, const adf_table_desc* d, const adf_table_step* st, long long n, hipStream_t s, float** result);
+// The program-driven loop (adf_sampler_run_program, adf_sampler.hip), in the same three parts.
+std::string program_refusal(const adf_prog_desc* d, const adf_prog_op* ops);
+void program_rows(const adf_prog_desc* d, const adf_prog_op* ops, std::vector<float>* rows);
+int run_program(adf_handle* h, Plan* p, const adf_prog_desc* d, const adf_prog_op* ops, long long n, hipStream_t s, float** result);
 
 }  // namespace adf_api

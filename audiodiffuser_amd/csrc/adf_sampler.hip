@@ -774,4 +774,81 @@ int run_table(adf_handle* h, Plan* p, const adf_table_desc* d, const adf_table_s
     return 0;
 }
 
+// ---- the program-driven loop (adf_sampler_run_program; the op form is in the header) -------------------------------------------------------------
+// VDPMSampler / VUniPCSampler (sampler_vobj.py:196-732) are linear multistep methods: a step reads the state and up to three earlier model outputs, the
+// UniPC corrector the one just computed as well.  The host resolves a run into a straight-line program over ADF_PROG_SLOTS state buffers
+// (audiodiffuser_amd/samplers.py); history rotation is slot renaming there, so this driver copies nothing and knows neither method.  No evaluation
+// touches Plan::sb (the guided one writes Plan::cfg_c / cfg_n), so the register file is sb[0 .. ADF_PROG_SLOTS).
+static_assert(ADF_PROG_SLOTS <= 10, "the register file is Plan::sb");
+static_assert(ADF_PROG_TERMS == 5, "launch_lin takes 1 to 5 operands");
+
+// Why the program cannot run, naming the argument, or "" (host only).
+std::string program_refusal(const adf_prog_desc* d, const adf_prog_op* ops) {
+    if (!d) return "desc is null";
+    if (!ops) return "ops is null";
+    if (d->num_ops <= 0) return "desc.num_ops = " + std::to_string(d->num_ops) + " must be positive";
+    if (!std::isfinite(d->x0_scale)) return "desc.x0_scale is not finite";
+    auto slot_ok = [](int k) { return k >= 0 && k < ADF_PROG_SLOTS; };
+    bool written[ADF_PROG_SLOTS] = {true};                   // slot 0 starts as x0_scale * noise
+    int n_eval = 0;
+    for (int i = 0; i < d->num_ops; ++i) {
+        const adf_prog_op& o = ops[i];
+        const std::string at = "ops[" + std::to_string(i) + "]";
+        if (o.kind != ADF_PROG_EVAL && o.kind != ADF_PROG_LIN) return at + ".kind = " + std::to_string(o.kind) + " is no ADF_PROG_* kind";
+        if (!slot_ok(o.dst)) return at + ".dst = " + std::to_string(o.dst) + " is outside the " + std::to_string(ADF_PROG_SLOTS) + " slots";
+        if (o.kind == ADF_PROG_EVAL) {
+            if (!slot_ok(o.src)) return at + ".src = " + std::to_string(o.src) + " is outside the " + std::to_string(ADF_PROG_SLOTS) + " slots";
+            if (!written[o.src]) return at + ".src reads slot " + std::to_string(o.src) + ", which nothing has written";
+            if (o.dst == o.src) return at + ": dst == src (an evaluation cannot overwrite its input)";
+            const adf_table_eval& e = o.eval;
+            if (!std::isfinite(e.c_in) || !std::isfinite(e.c_noise) || !std::isfinite(e.c_skip) || !std::isfinite(e.c_out))
+                return at + ".eval holds a non-finite row entry";
+            if (e.clip != ADF_CLIP_NONE && e.clip != ADF_CLIP_CONFIGURED && e.clip != ADF_CLIP_UNIT) return at + ".eval.clip is no ADF_CLIP_* mode";
+            ++n_eval;
+        } else {
+            if (o.n_terms < 1 || o.n_terms > ADF_PROG_TERMS)
+                return at + ".n_terms = " + std::to_string(o.n_terms) + " is outside 1 .. " + std::to_string(ADF_PROG_TERMS);
+            for (int j = 0; j < o.n_terms; ++j) {
+                const std::string tj = at + ".slot[" + std::to_string(j) + "]";
+                if (!slot_ok(o.slot[j])) return tj + " = " + std::to_string(o.slot[j]) + " is outside the " + std::to_string(ADF_PROG_SLOTS) + " slots";
+                if (!written[o.slot[j]]) return tj + " reads slot " + std::to_string(o.slot[j]) + ", which nothing has written";
+                for (int k = 0; k < j; ++k)
+                    if (o.slot[k] == o.slot[j]) return tj + " names slot " + std::to_string(o.slot[j]) + " a second time";
+                if (!std::isfinite(o.coef[j])) return at + ".coef[" + std::to_string(j) + "] is not finite";
+            }
+        }
+        written[o.dst] = true;
+    }
+    if (!slot_ok(d->result_slot)) return "desc.result_slot = " + std::to_string(d->result_slot) + " is outside the " + std::to_string(ADF_PROG_SLOTS) + " slots";
+    if (!written[d->result_slot]) return "desc.result_slot reads slot " + std::to_string(d->result_slot) + ", which nothing has written";
+    if (n_eval == 0) return "ops hold no ADF_PROG_EVAL: a program without an evaluation is no sampler";
+    return "";
+}
+
+// the rows of every evaluation of the program, in order (four floats each)
+void program_rows(const adf_prog_desc* d, const adf_prog_op* ops, std::vector<float>* rows) {
+    rows->clear();
+    for (int i = 0; i < d->num_ops; ++i)
+        if (ops[i].kind == ADF_PROG_EVAL) rows->insert(rows->end(), {ops[i].eval.c_in, ops[i].eval.c_noise, ops[i].eval.c_skip, ops[i].eval.c_out});
+}
+
+int run_program(adf_handle* h, Plan* p, const adf_prog_desc* d, const adf_prog_op* ops, long long n, hipStream_t s, float** result) {
+    if (const char* e = launch_scale(p->sb[0], p->noise_stage, d->x0_scale, n, s)) return fail(h, e);
+    int k = 0;
+    for (int i = 0; i < d->num_ops; ++i) {
+        const adf_prog_op& o = ops[i];
+        if (o.kind == ADF_PROG_EVAL) {
+            if (table_eval(h, p, k++, o.eval, p->sb[o.src], p->sb[o.dst], s)) return 1;
+            continue;
+        }
+        LinTerms t;
+        memset(&t, 0, sizeof(t));
+        t.n = o.n_terms;
+        for (int j = 0; j < o.n_terms; ++j) { t.p[j] = p->sb[o.slot[j]]; t.k[j] = o.coef[j]; }
+        if (const char* e = launch_lin(p->sb[o.dst], t, o.clamp != 0, n, s)) return fail(h, e);
+    }
+    *result = p->sb[d->result_slot];
+    return 0;
+}
+
 }  // namespace adf_api

@@ -291,9 +291,9 @@ class VDiffusion(Diffusion):
     """v-prediction (diffusion.py:260-365).  ``for_edm=True`` wraps the v network as an x0 denoiser over sigma = sigma_t / alpha_t, which
     is what the ``sampler_edm`` samplers drive: ``alpha_t x_in - sigma_t v`` with ``x_in = alpha_t x`` and ``alpha_t = sqrt(sigmoid(-2 ln sigma))``,
     returned unclipped (``dynamic_threshold`` is stored and never read, as in the reference).  ``for_edm=False`` returns the raw v prediction
-    at the given log-SNR for the reference's ``sampler_vobj`` samplers.  Of those ``VSampler`` and ``VEulerSampler`` are built (samplers.py) and run
-    it on the device through rows of their own; ``denoise_fn`` called directly, and every other sampler given it, take the compatibility branch as before
-    (``sampler_vobj.DPMSampler`` / ``UniPCSampler`` are not built)."""
+    at the given log-SNR for the reference's ``sampler_vobj`` samplers.  All four are built (samplers.py: ``VSampler``, ``VEulerSampler``, ``VDPMSampler``,
+    ``VUniPCSampler``) and run it on the device through rows of their own; ``denoise_fn`` called directly, and every other sampler given it, take the
+    compatibility branch as before."""
 
     _clips = False
 
@@ -305,8 +305,8 @@ class VDiffusion(Diffusion):
         return (_lib.PRECOND_V_EDM, 0.0, 1.0, 1.0) if self.for_edm else None
 
     def _not_native_note(self) -> str:
-        return ("" if self.for_edm else ": VDiffusion(for_edm=False) feeds the reference's sampler_vobj.DPMSampler / sampler_vobj.UniPCSampler, "
-                "which are not built; only for_edm=True has a device form")
+        return ("" if self.for_edm else ": VDiffusion(for_edm=False) returns the raw v, which only the sampler_vobj samplers take -- VSampler, VEulerSampler, "
+                "VDPMSampler and VUniPCSampler run it on the device through rows of their own; for every other caller only for_edm=True has a device form")
 
     # diffusion.py:282-285
     def shifted_cosine_transform(self, t: Tensor) -> Tensor:

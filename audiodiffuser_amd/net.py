@@ -213,6 +213,19 @@ class NativeHandle:
                                                       C.c_void_p(_stream_ptr(noise.device))), "adf_sampler_run_table")
         return out
 
+    def sampler_run_program(self, desc: "_lib.AdfProgDesc", ops, noise: torch.Tensor) -> torch.Tensor:
+        """``adf_sampler_run_program``: ``ops`` is a ctypes array of ``desc.num_ops`` ``AdfProgOp``; a None ``desc`` or ``ops`` goes through as a null pointer,
+        which the library refuses."""
+        out = torch.empty_like(noise)
+        if desc is not None and ops is not None and len(ops) < desc.num_ops:
+            raise ValueError(f"the program holds {len(ops)} ops, desc.num_ops is {desc.num_ops}")
+        with torch.cuda.device(noise.device):
+            self.check(self.lib.adf_sampler_run_program(self.h, C.byref(desc) if desc is not None else None, ops, C.c_void_p(noise.data_ptr()),
+                                                        C.c_void_p(out.data_ptr()),
+                                                        noise.shape[0], self._length(noise), C.c_void_p(_stream_ptr(noise.device))),
+                       "adf_sampler_run_program")
+        return out
+
     def counters(self) -> Dict[str, int]:
         """What the device loop has done so far (``adf_get_counters``): sampler runs, evaluations, graph captures / replays."""
         c = _lib.AdfRunCounters()

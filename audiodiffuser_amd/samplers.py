@@ -12,6 +12,9 @@ callable the same recurrences are expressed with tensor ops around ``fn`` (inter
 ``VESampler`` / ``VPSampler`` (sampler_edm.py:31-227) and ``VSampler`` / ``VEulerSampler`` (sampler_vobj.py:31-194) go one step further: the host
 resolves a run into a table with one record per step -- coefficients of a few whole-state linear combinations and the rows of the step's one or two
 denoiser evaluations -- and one generic device loop runs it (``adf_sampler_run_table``; ``_TableSampler`` below).
+
+``VDPMSampler`` / ``VUniPCSampler`` (sampler_vobj.py:196-732) are linear multistep methods: their runs are resolved into a straight-line program over a
+few state buffers (``adf_sampler_run_program``; ``_VObjProgramSampler`` at the end of this file).
 """
 from __future__ import annotations
 
@@ -1020,5 +1023,488 @@ class UniPCSampler(_Sampler):
                 gl[i], ml[i] = gl[i + 1], ml[i + 1]
             gl[-1] = grid[step]
             if step < steps:
+                ml[-1] = m
+        return x.clamp(-1.0, 1.0)
+
+
+class _VObjProgramSampler(_VObjTableSampler):
+    """What ``VDPMSampler`` and ``VUniPCSampler`` share (sampler_vobj.py:196-732): linear multistep methods over the raw v of a
+    ``VDiffusion(for_edm=False)``.  A step reads the state and up to three earlier model outputs, so the per-step record of ``_TableSampler`` cannot
+    hold them; the host resolves a run into a straight-line program over a few state buffers instead (``adf_prog_op``,
+    include/audiodiffuser_amd.h) and the device runs it (``adf_sampler_run_program``).  ``_scalars`` gives the reference's fp32 scalars (its own torch
+    op sequence on CPU tensors), ``_program`` combines them in double into the ops; the history of a method is renamed from step to step, never copied.
+
+    Both samplers read ``sigmas[0]`` and ``sigmas[-1]`` only, map them through the shifted cosine transform with the hard-wired
+    ``logsnr_min = -15, logsnr_max = 15, shift = 0`` (:227-233, :540-546) and walk ``linspace`` between the two; ``sigma(l) = sqrt(sigmoid(-l))`` is the
+    noise level, ``sigma(-l)`` is alpha, and every step width enters halved.  The model output ``alpha x - sigma v`` (``x0_pred``) or
+    ``sigma x + alpha v`` is one evaluation with the row (1, l, alpha, -sigma) or (1, l, sigma, alpha) and no clip: the epilogue writes it."""
+
+    logsnr_min, logsnr_max, shift = -15, 15, 0.0
+    _MAX_ORDER = 3
+
+    @staticmethod
+    def _sig(l: Tensor) -> Tensor:
+        return torch.sqrt(torch.sigmoid(-l))
+
+    def _grid(self, sigmas: Tensor, n: int) -> Tensor:
+        s = sigmas.detach().to("cpu", torch.float32)
+        return torch.linspace(self.shifted_cosine_transform(s[0]), self.shifted_cosine_transform(s[-1]), n + 1)
+
+    def _row(self, l: float) -> "_lib.AdfTableEval":
+        """The model output at log-SNR ``l`` as one row; alpha and sigma as the reference forms them in fp32."""
+        t = torch.tensor(l, dtype=torch.float32)
+        sig, alp = float(self._sig(t)), float(self._sig(-t))
+        return self._eval(1.0, l, alp, -sig, _lib.CLIP_NONE) if self.x0_pred else self._eval(1.0, l, sig, alp, _lib.CLIP_NONE)
+
+    @staticmethod
+    def _ev(dst: int, src: int, e: "_lib.AdfTableEval") -> "_lib.AdfProgOp":
+        return _lib.AdfProgOp(kind=_lib.PROG_EVAL, dst=dst, src=src, eval=e)
+
+    @staticmethod
+    def _lin(dst: int, terms, clamp: bool = False) -> "_lib.AdfProgOp":
+        """``terms``: (slot, coefficient) pairs; a slot named twice is summed here (in double), a zero coefficient is not an operand."""
+        acc = {}
+        for slot, k in terms:
+            acc[slot] = acc.get(slot, 0.0) + float(k)
+        acc = [(s, k) for s, k in acc.items() if k != 0.0] or [(terms[0][0], 0.0)]
+        op = _lib.AdfProgOp(kind=_lib.PROG_LIN, dst=dst, n_terms=len(acc), clamp=int(clamp))
+        for j, (s, k) in enumerate(acc):
+            op.slot[j], op.coef[j] = s, k
+        return op
+
+    def _class_drop(self) -> Optional[str]:
+        """Why this run cannot be native on a class-conditional net (the reference drops ``classes`` on some evaluations), or None."""
+        raise NotImplementedError
+
+    def _owner(self, fn: Callable, net, kwargs: dict, noise: Tensor) -> Optional[VDiffusion]:
+        owner = super()._owner(fn, net, kwargs, noise)
+        if owner is None:
+            return None
+        why = None
+        if not 1 <= self.order <= self._MAX_ORDER:
+            why = f"order = {self.order}: the device program covers orders 1 to {self._MAX_ORDER}"
+        elif net.cfg.class_cond:
+            why = self._class_drop()
+        if why is None:
+            return owner
+        self._refuse(why)
+        return None
+
+    def _run_program(self, noise: Tensor, net, kwargs: dict, ops: list, x0_scale: float, result_slot: int) -> Tensor:
+        x = _prep(noise)
+        hd = net.native(x.device)
+        if net.cfg.class_cond:
+            hd.set_condition(kwargs["classes"], x.device, null_labels=False, cond_scale=float(self.cond_scale))
+        desc = _lib.AdfProgDesc(num_ops=len(ops), result_slot=result_slot, x0_scale=x0_scale, use_graph=int(self.use_graph))
+        return hd.sampler_run_program(desc, (_lib.AdfProgOp * len(ops))(*ops), x).to(noise.dtype)
+
+    @torch.no_grad()
+    def forward(self, noise: Tensor, fn: Callable, net: nn.Module, sigmas: Tensor, **kwargs) -> Tensor:
+        self._check()
+        if self._owner(fn, net, kwargs, noise) is not None:
+            ops, x0_scale, result = self._program(sigmas)
+            return self._run_program(noise, net, kwargs, ops, x0_scale, result)
+        return self._compat(noise, fn, net, sigmas, kwargs)
+
+
+class VDPMSampler(_VObjProgramSampler):
+    """``sampler_vobj.DPMSampler`` (sampler_vobj.py:196-499): DPM-Solver in the halved log-SNR, orders 1 to 3, single-step ("DPM-Solver-fast", the
+    order list ``[3] * (K - 2) + [2, 1]`` etc. of :465-481) or multistep; the start state is ``noise`` itself, the result is clamped.  What the
+    reference does and this class keeps: the single-step inner evaluations are called without ``**kwargs`` (``classes`` reaches only the first
+    evaluation of a step, :286-314); the multistep order-1 update calls ``fn`` and discards the result whenever the model output is handed in (:323,
+    one dead network pass at step 1 and one at every trailing order-1 step).  The device program skips the dead passes -- they change nothing -- and
+    the tensor-op branch makes them."""
+
+    def __init__(self, cond_scale, order=1, num_steps=10, multisteps=False, x0_pred: bool = True, use_graph: bool = True):
+        super().__init__()
+        self.order, self.num_steps, self.cond_scale, self.multisteps, self.x0_pred, self.use_graph = order, num_steps, cond_scale, multisteps, x0_pred, use_graph
+
+    def _check(self) -> None:
+        if self.multisteps:
+            assert self.num_steps >= self.order                                           # :401
+        elif self.order not in (1, 2, 3):
+            raise ValueError("'order' must be '1' or '2' or '3'.")                        # :483
+
+    def singlestep_orders(self):
+        """(orders, K) of sampler_vobj.py:465-481."""
+        n, order = self.num_steps, self.order
+        if order == 3:
+            k = n // 3 + 1
+            return ([3] * (k - 2) + [2, 1] if n % 3 == 0 else [3] * (k - 1) + [n % 3]), k
+        if order == 2:
+            return ([2] * (n // 2), n // 2) if n % 2 == 0 else ([2] * (n // 2) + [1], n // 2 + 1)
+        return [1] * n, n
+
+    def multistep_orders(self):
+        """The order of the update into grid point 1 .. num_steps (:423-452)."""
+        n, order = self.num_steps, self.order
+        return [step if step < order else min(order, n + 1 - step) for step in range(1, n + 1)]
+
+    def _class_drop(self) -> Optional[str]:
+        if self.multisteps or all(o == 1 for o in self.singlestep_orders()[0]):
+            return None
+        return ("the reference drops `classes` on the inner evaluations of a single-step update of order 2 or 3 (sampler_vobj.py:286-314): "
+                "a class-conditional run is native in multistep mode or with an all-order-1 list")
+
+    def _scalars(self, sigmas: Tensor) -> dict:
+        """``grid`` (the log-SNR list) and per step the reference's fp32 scalars as Python floats, each formed by its own sequence of torch
+        operations on 0-dim CPU tensors: ``l`` the log-SNRs the step evaluates at, ``A`` the coefficient of x and the products in front of the model
+        outputs / differences, per intermediate state (single-step) or per update (multistep)."""
+        sig, x0 = self._sig, self.x0_pred
+        num = (lambda l: sig(l)) if x0 else (lambda l: sig(-l))               # the factor in front of x: sigma ratio (x0) or alpha ratio
+        fac = (lambda l: sig(-l)) if x0 else (lambda l: sig(l))               # the factor in front of the model output: alpha (x0) or sigma
+        em = (lambda v: torch.expm1(-v)) if x0 else (lambda v: torch.expm1(v))
+        fl = lambda d: {k: ([float(u) for u in v] if isinstance(v, (list, tuple)) else v if isinstance(v, int) else float(v)) for k, v in d.items()}
+        steps = []
+        if not self.multisteps:
+            orders, k = self.singlestep_orders()
+            grid = self._grid(sigmas, k)
+            for i, o in enumerate(orders):
+                lc, ln = grid[i], grid[i + 1]
+                h = ln - lc
+                if o == 1:
+                    h = h / 2
+                    rec = dict(order=1, l=[lc], A3=num(ln) / num(lc), B3=fac(ln) * em(h))
+                elif o == 2:
+                    r1 = 1 / 2
+                    s1 = lc + r1 * h
+                    h = h / 2
+                    rec = dict(order=2, l=[lc, s1], A1=num(s1) / num(lc), B1=fac(s1) * em(r1 * h), A3=num(ln) / num(lc), B3=fac(ln) * em(h),
+                               C3=fac(ln) / (2 * r1) * em(h))
+                else:
+                    r1, r2 = 1 / 3, 2 / 3
+                    s1 = lc + r1 * h
+                    s2 = lc + r2 * h
+                    h = h / 2
+                    if x0:
+                        c2 = sig(-s2) * (r2 / r1) * ((-r2 * h).expm1() / (r2 * h) + 1)
+                        c3 = sig(-ln) * 1 / r2 * (torch.expm1(-h) / h + 1)
+                    else:
+                        c2 = sig(s2) * (r2 / r1) * ((r2 * h).expm1() / (r2 * h) - 1)
+                        c3 = sig(ln) / r2 * (h.expm1() / h - 1)
+                    rec = dict(order=3, l=[lc, s1, s2], A1=num(s1) / num(lc), B1=fac(s1) * em(r1 * h), A2=num(s2) / num(lc), B2=fac(s2) * em(r2 * h),
+                               C2=c2, A3=num(ln) / num(lc), B3=fac(ln) * em(h), C3=c3)
+                steps.append(fl(rec))
+            return dict(grid=[float(v) for v in grid], steps=steps)
+        grid = self._grid(sigmas, self.num_steps)
+        for step, o in enumerate(self.multistep_orders(), start=1):
+            lc, l0 = grid[step], grid[step - 1]
+            h = lc - l0
+            rec = dict(order=o, l=[lc] if step < self.num_steps else [])
+            if o >= 2:
+                rec["inv_r0"] = 1. / ((l0 - grid[step - 2]) / h)
+            if o == 3:
+                r0, r1 = (l0 - grid[step - 2]) / h, (grid[step - 2] - grid[step - 3]) / h
+                rec.update(inv_r1=1. / r1, q=r0 / (r0 + r1), w=1. / (r0 + r1))
+            h = h / 2
+            phi1 = em(h)
+            rec.update(A=num(lc) / num(l0), B=fac(lc) * phi1)
+            if o == 2:
+                rec["C"] = fac(lc) * 0.5 * phi1 if x0 else 0.5 * (fac(lc) * phi1)
+            if o == 3:
+                phi2 = phi1 / h + 1. if x0 else phi1 / h - 1.
+                phi3 = phi2 / h - 0.5
+                rec.update(P2=fac(lc) * phi2, P3=fac(lc) * phi3)
+            steps.append(fl(rec))
+        return dict(grid=[float(v) for v in grid], steps=steps)
+
+    def _program(self, sigmas: Tensor):
+        """(ops, x0_scale, result slot).  Single-step: x in slot 0, the step's model outputs in 1, 3, 4 and its intermediate state in 2.  Multistep: x in
+        slot 0, the history in slots renamed from step to step; the discarded evaluations of the reference are not part of the program."""
+        sc, x0 = self._scalars(sigmas), self.x0_pred
+        ops, n = [], len(sc["steps"])
+        if not self.multisteps:
+            X, E0, U, E1, E2 = 0, 1, 2, 3, 4
+            for i, r in enumerate(sc["steps"]):
+                last = i + 1 == n
+                ops.append(self._ev(E0, X, self._row(r["l"][0])))
+                if r["order"] == 1:
+                    ops.append(self._lin(X, [(X, r["A3"]), (E0, -r["B3"])], last))
+                    continue
+                ops += [self._lin(U, [(X, r["A1"]), (E0, -r["B1"])]), self._ev(E1, U, self._row(r["l"][1]))]
+                if r["order"] == 2:
+                    ops.append(self._lin(X, [(X, r["A3"]), (E0, -r["B3"] + r["C3"]), (E1, -r["C3"])], last))
+                    continue
+                s = 1.0 if x0 else -1.0                                     # the sign of the difference terms (:306-315)
+                ops += [self._lin(U, [(X, r["A2"]), (E0, -r["B2"] - s * r["C2"]), (E1, s * r["C2"])]), self._ev(E2, U, self._row(r["l"][2])),
+                        self._lin(X, [(X, r["A3"]), (E0, -r["B3"] - s * r["C3"]), (E2, s * r["C3"])], last)]
+            return ops, 1.0, 0
+        X, free, hist = 0, [1, 2, 3, 4], []
+        hist.append(free.pop(0))
+        ops.append(self._ev(hist[-1], X, self._row(sc["grid"][0])))
+        for step, r in enumerate(sc["steps"], start=1):
+            o = r["order"]
+            m = hist[::-1]                                                  # m[0] the newest
+            if o == 1:
+                terms = [(m[0], -r["B"])]
+            elif o == 2:
+                terms = [(m[0], -r["B"] - r["C"] * r["inv_r0"]), (m[1], r["C"] * r["inv_r0"])]
+            else:
+                i0, i1, q, w = r["inv_r0"], r["inv_r1"], r["q"], r["w"]
+                e = (i0, -(i0 + i1), i1)                                    # D1_0 - D1_1 over (m0, m1, m2)
+                d1 = (i0 + q * e[0], -i0 + q * e[1], q * e[2])
+                s = 1.0 if x0 else -1.0
+                terms = [(m[j], (-r["B"] if j == 0 else 0.0) + s * r["P2"] * d1[j] - r["P3"] * w * e[j]) for j in range(3)]
+            ops.append(self._lin(X, [(X, r["A"])] + terms, step == n))
+            if step < n:
+                if len(hist) == self.order:
+                    free.append(hist.pop(0))
+                hist.append(free.pop(0))
+                ops.append(self._ev(hist[-1], X, self._row(r["l"][0])))
+        return ops, 1.0, 0
+
+    def _compat(self, noise, fn, net, sigmas, kwargs):
+        """sampler_vobj.py:389-499 as written, dead calls and dropped keywords included."""
+        sig, x0 = self._sig, self.x0_pred
+        call = lambda x_, l, **kw: fn(x_, net=net, sigma=l, inference=True, cond_scale=self.cond_scale, **kw)
+
+        def model(x_, l, **kw):
+            v = call(x_, l, **kw)
+            return sig(-l) * x_ - sig(l) * v if x0 else sig(l) * x_ + sig(-l) * v
+
+        x = noise
+        l_start, l_end = self.shifted_cosine_transform(sigmas[0]), self.shifted_cosine_transform(sigmas[-1])
+        if not self.multisteps:
+            orders, k = self.singlestep_orders()
+            grid = torch.linspace(l_start, l_end, k + 1, device=x.device)
+            for i, o in enumerate(orders):
+                lc, ln = grid[i], grid[i + 1]
+                eps = model(x, lc, **kwargs)
+                h = ln - lc
+                if o == 1:
+                    h = h / 2
+                    x = sig(ln) / sig(lc) * x - sig(-ln) * (-h).expm1() * eps if x0 else sig(-ln) / sig(-lc) * x - sig(ln) * h.expm1() * eps
+                elif o == 2:
+                    r1 = 1 / 2
+                    s1 = lc + r1 * h
+                    h = h / 2
+                    if x0:
+                        u1 = sig(s1) / sig(lc) * x - sig(-s1) * torch.expm1(-r1 * h) * eps
+                        e1 = model(u1, s1)
+                        x = sig(ln) / sig(lc) * x - sig(-ln) * torch.expm1(-h) * eps - sig(-ln) / (2 * r1) * torch.expm1(-h) * (e1 - eps)
+                    else:
+                        u1 = sig(-s1) / sig(-lc) * x - sig(s1) * (r1 * h).expm1() * eps
+                        e1 = model(u1, s1)
+                        x = sig(-ln) / sig(-lc) * x - sig(ln) * h.expm1() * eps - sig(ln) / (2 * r1) * h.expm1() * (e1 - eps)
+                else:
+                    r1, r2 = 1 / 3, 2 / 3
+                    s1 = lc + r1 * h
+                    s2 = lc + r2 * h
+                    h = h / 2
+                    if x0:
+                        u1 = sig(s1) / sig(lc) * x - sig(-s1) * (-r1 * h).expm1() * eps
+                        e1 = model(u1, s1)
+                        u2 = (sig(s2) / sig(lc) * x - sig(-s2) * (-r2 * h).expm1() * eps
+                              + sig(-s2) * (r2 / r1) * ((-r2 * h).expm1() / (r2 * h) + 1) * (e1 - eps))
+                        e2 = model(u2, s2)
+                        x = sig(ln) / sig(lc) * x - sig(-ln) * torch.expm1(-h) * eps + sig(-ln) * 1 / r2 * (torch.expm1(-h) / h + 1) * (e2 - eps)
+                    else:
+                        u1 = sig(-s1) / sig(-lc) * x - sig(s1) * (r1 * h).expm1() * eps
+                        e1 = model(u1, s1)
+                        u2 = (sig(-s2) / sig(-lc) * x - sig(s2) * (r2 * h).expm1() * eps
+                              - sig(s2) * (r2 / r1) * ((r2 * h).expm1() / (r2 * h) - 1) * (e1 - eps))
+                        e2 = model(u2, s2)
+                        x = sig(-ln) / sig(-lc) * x - sig(ln) * h.expm1() * eps - sig(ln) / r2 * (h.expm1() / h - 1) * (e2 - eps)
+            return x.clamp(-1.0, 1.0)
+
+        def update(x_, o, ml, ll, lc):
+            l0, m0 = ll[-1], ml[-1]
+            h = lc - l0
+            if o == 1:
+                h = h / 2
+                call(x_, l0, **kwargs)                                      # :323: evaluated and discarded, the model output is handed in
+                phi1 = torch.expm1(-h) if x0 else torch.expm1(h)
+                return sig(lc) / sig(l0) * x_ - sig(-lc) * phi1 * m0 if x0 else sig(-lc) / sig(-l0) * x_ - sig(lc) * phi1 * m0
+            if o == 2:
+                r0 = (l0 - ll[-2]) / h
+                d10 = (1. / r0) * (m0 - ml[-2])
+                h = h / 2
+                if x0:
+                    phi1 = torch.expm1(-h)
+                    return sig(lc) / sig(l0) * x_ - sig(-lc) * phi1 * m0 - sig(-lc) * 0.5 * phi1 * d10
+                phi1 = torch.expm1(h)
+                return sig(-lc) / sig(-l0) * x_ - (sig(lc) * phi1) * m0 - 0.5 * (sig(lc) * phi1) * d10
+            if o == 3:
+                l2, l1, l0 = ll                                             # exactly three entries, as the reference unpacks them (:360)
+                m2, m1, m0 = ml
+                r0, r1 = (l0 - l1) / h, (l1 - l2) / h
+                h = h / 2
+                d10, d11 = (1. / r0) * (m0 - m1), (1. / r1) * (m1 - m2)
+                d1 = d10 + (r0 / (r0 + r1)) * (d10 - d11)
+                d2 = (1. / (r0 + r1)) * (d10 - d11)
+                if x0:
+                    phi1 = torch.expm1(-h)
+                    phi2 = phi1 / h + 1.
+                    phi3 = phi2 / h - 0.5
+                    return sig(lc) / sig(l0) * x_ - sig(-lc) * phi1 * m0 + sig(-lc) * phi2 * d1 - sig(-lc) * phi3 * d2
+                phi1 = torch.expm1(h)
+                phi2 = phi1 / h - 1.
+                phi3 = phi2 / h - 0.5
+                return sig(-lc) / sig(-l0) * x_ - (sig(lc) * phi1) * m0 - (sig(lc) * phi2) * d1 - (sig(lc) * phi3) * d2
+            return x_                                                       # no branch of :446-452 matches an order above 3
+
+        n, order = self.num_steps, self.order
+        grid = torch.linspace(l_start, l_end, n + 1, device=x.device)
+        ml, ll = [model(x, grid[0], **kwargs)], [grid[0]]
+        for step in range(1, order):
+            x = update(x, step, ml, ll, grid[step])
+            ll.append(grid[step])
+            ml.append(model(x, grid[step], **kwargs))
+        for step in range(order, n + 1):
+            x = update(x, min(order, n + 1 - step), ml, ll, grid[step])
+            for i in range(order - 1):
+                ll[i], ml[i] = ll[i + 1], ml[i + 1]
+            ll[-1] = grid[step]
+            if step < n:
+                ml[-1] = model(x, grid[step], **kwargs)
+        return x.clamp(-1.0, 1.0)
+
+
+class VUniPCSampler(_VObjProgramSampler):
+    """``sampler_vobj.UniPCSampler`` (sampler_vobj.py:502-732, variant 'bh2'): multistep predictor-corrector in the halved log-SNR, one corrector
+    evaluation per step except the last (NFE = ``num_steps``); the start state is ``sigmas[0] * noise``, the result is clamped.  What the reference
+    does and this class keeps: the corrector's evaluation gets no keywords (``forward`` hands none to ``multistep_uni_pc_update``, :694, :715); with
+    ``x0_pred`` the corrector line lacks the alpha factor the predictor has (:644 against :634); for order 3 ``rhos_p`` / ``rhos_c`` come from
+    ``torch.linalg.solve`` in fp32.  The reference's ``einsum('k,bkchw->bchw')`` runs orders >= 2 on 4-D states only; here any rank works and on 4-D
+    input the result is the reference's."""
+
+    def __init__(self, num_steps: int = 20, order: int = 2, cond_scale: float = 1.0, x0_pred: bool = True, use_graph: bool = True):
+        super().__init__()
+        self.num_steps, self.order, self.cond_scale, self.x0_pred, self.use_graph = num_steps, order, cond_scale, x0_pred, use_graph
+
+    def _check(self) -> None:
+        assert self.num_steps >= self.order                                               # :677
+
+    def update_plan(self):
+        """(order, corrector?) of the update into grid point 1 .. num_steps (:692-719)."""
+        n, order = self.num_steps, self.order
+        return [(step, True) if step < order else (min(order, n + 1 - step), step != n) for step in range(1, n + 1)]
+
+    def _class_drop(self) -> Optional[str]:
+        if not any(corr for _, corr in self.update_plan()):
+            return None
+        return ("the reference drops `classes` on every corrector evaluation (sampler_vobj.py:694, :715 hand multistep_uni_pc_update no keywords): "
+                "a class-conditional run is native only without one (num_steps = 1)")
+
+    def _update_scalars(self, ll: list, lc: Tensor, o: int, corr: bool) -> dict:
+        """multistep_uni_pc_update (:551-668) up to the state arithmetic: every scalar on fp32 tensors in the reference's order."""
+        sig, x0 = self._sig, self.x0_pred
+        lc = lc.view(-1)
+        l0 = ll[-1]
+        h = lc - l0
+        rks = [(ll[-(i + 1)] - l0) / h for i in range(1, o)]
+        rk_t = torch.tensor([float(r) for r in rks] + [1.], dtype=torch.float32)
+        hh = -h / 2 if x0 else h / 2
+        h_phi_1 = torch.expm1(hh)
+        h_phi_k = h_phi_1 / hh - 1
+        fact, b_h = 1, torch.expm1(hh)
+        R, b = [], []
+        for i in range(1, o + 1):
+            R.append(torch.pow(rk_t, i - 1))
+            b.append(h_phi_k * fact / b_h)
+            fact *= (i + 1)
+            h_phi_k = h_phi_k / hh - 1 / fact
+        R, b = torch.stack(R), torch.cat(b)
+        rhos_p = [] if o == 1 else torch.tensor([0.5]) if o == 2 else torch.linalg.solve(R[:-1, :-1], b[:-1])
+        rhos_c = [] if not corr else torch.tensor([0.5]) if o == 1 else torch.linalg.solve(R, b)
+        f = sig(-lc) if x0 else sig(lc)
+        A = sig(lc) / sig(l0) if x0 else sig(-lc) / sig(-l0)
+        return dict(order=o, corr=int(corr), l=float(lc), A=float(A), M0=float(f * h_phi_1), PB=float(f * b_h), CB=float(b_h if x0 else f * b_h),
+                    rks=[float(r) for r in rks], rhos_p=[float(r) for r in rhos_p], rhos_c=[float(r) for r in rhos_c])
+
+    def _scalars(self, sigmas: Tensor) -> dict:
+        """``grid``, ``x0_scale`` (= sigmas[0]) and per update the reference's fp32 scalars as Python floats: the coefficient ``A`` of x, the products
+        ``M0`` (in front of the newest model output), ``PB`` / ``CB`` (in front of the predictor's / corrector's history sum), ``rks`` and the
+        ``rhos_p`` / ``rhos_c`` it solves for."""
+        grid = self._grid(sigmas, self.num_steps)
+        steps = [self._update_scalars([grid[j] for j in range(max(0, step - self.order), step)], grid[step], o, corr)
+                 for step, (o, corr) in enumerate(self.update_plan(), start=1)]
+        return dict(grid=[float(v) for v in grid], x0_scale=float(sigmas.detach().to("cpu", torch.float32)[0]), steps=steps)
+
+    def _program(self, sigmas: Tensor):
+        """(ops, x0_scale, result slot): x in slot 0, the predictor's state in slot 1, the history and the corrector's model output in slots 2 .. 5,
+        renamed from step to step.  The corrected state is one update over x, the history and the new output: five operands at order 3."""
+        sc = self._scalars(sigmas)
+        X, P, free, hist = 0, 1, [2, 3, 4, 5], []
+        hist.append(free.pop(0))
+        ops, n = [self._ev(hist[-1], X, self._row(sc["grid"][0]))], len(sc["steps"])
+        for step, r in enumerate(sc["steps"], start=1):
+            m = hist[::-1]                                                  # m[0] the newest, m[k + 1] goes with rks[k]
+            kk = range(r["order"] - 1)
+            pred = [(X, r["A"]), (m[0], -r["M0"] + r["PB"] * sum(r["rhos_p"][k] / r["rks"][k] for k in kk))]
+            pred += [(m[k + 1], -r["PB"] * r["rhos_p"][k] / r["rks"][k]) for k in kk]
+            if not r["corr"]:
+                ops.append(self._lin(X, pred, step == n))
+            else:
+                rc, cb = r["rhos_c"], r["CB"]
+                mt = free.pop(0)
+                corr = [(X, r["A"]), (m[0], -r["M0"] + cb * (sum(rc[k] / r["rks"][k] for k in kk) + rc[-1]))]
+                corr += [(m[k + 1], -cb * rc[k] / r["rks"][k]) for k in kk] + [(mt, -cb * rc[-1])]
+                ops += [self._lin(P, pred), self._ev(mt, P, self._row(r["l"])), self._lin(X, corr, step == n)]
+                if step >= self.order and len(hist) == self.order:
+                    free.append(hist.pop(0))
+                hist.append(mt)
+        return ops, sc["x0_scale"], X
+
+    def _compat(self, noise, fn, net, sigmas, kwargs):
+        """sampler_vobj.py:670-732 and :551-668 as written; the history sums are plain sums, so any rank of state works."""
+        sig, x0 = self._sig, self.x0_pred
+
+        def model(x_, l, **kw):
+            v = fn(x_, net=net, sigma=l, inference=True, cond_scale=self.cond_scale, **kw)
+            return sig(-l) * x_ - sig(l) * v if x0 else sig(l) * x_ + sig(-l) * v
+
+        def update(x_, ml, ll, lc, o, corr):
+            lc = lc.view(-1)
+            l0, m0 = ll[-1], ml[-1]
+            h = lc - l0
+            rks, d1s = [], []
+            for i in range(1, o):
+                rk = (ll[-(i + 1)] - l0) / h
+                rks.append(rk)
+                d1s.append((ml[-(i + 1)] - m0) / rk)
+            rks = torch.tensor([float(r) for r in rks] + [1.], device=x_.device)
+            hh = -h / 2 if x0 else h / 2
+            h_phi_1 = torch.expm1(hh)
+            h_phi_k, b_h, fact = h_phi_1 / hh - 1, torch.expm1(hh), 1
+            R, b = [], []
+            for i in range(1, o + 1):
+                R.append(torch.pow(rks, i - 1))
+                b.append(h_phi_k * fact / b_h)
+                fact *= (i + 1)
+                h_phi_k = h_phi_k / hh - 1 / fact
+            R, b = torch.stack(R), torch.cat(b)
+            comb = lambda rho: sum(rho[k] * d for k, d in enumerate(d1s)) if d1s else 0
+            rho_p = (torch.tensor([0.5], device=b.device) if o == 2 else torch.linalg.solve(R[:-1, :-1], b[:-1])) if d1s else None
+            if corr:
+                rho_c = torch.tensor([0.5], device=b.device) if o == 1 else torch.linalg.solve(R, b)
+            if x0:
+                xt_ = sig(lc) / sig(l0) * x_ - sig(-lc) * h_phi_1 * m0
+                x_t, m_t = xt_ - sig(-lc) * b_h * comb(rho_p), None
+                if corr:
+                    m_t = model(x_t, lc[0])                                 # no keywords (:637)
+                    x_t = xt_ - b_h * (comb(rho_c[:-1]) + rho_c[-1] * (m_t - m0))          # no alpha factor (:644)
+            else:
+                xt_ = sig(-lc) / sig(-l0) * x_ - sig(lc) * h_phi_1 * m0
+                x_t, m_t = xt_ - sig(lc) * b_h * comb(rho_p), None
+                if corr:
+                    m_t = model(x_t, lc[0])
+                    x_t = xt_ - sig(lc) * b_h * (comb(rho_c[:-1]) + rho_c[-1] * (m_t - m0))
+            return x_t, m_t
+
+        n, order = self.num_steps, self.order
+        x = sigmas[0] * noise
+        grid = torch.linspace(self.shifted_cosine_transform(sigmas[0]), self.shifted_cosine_transform(sigmas[-1]), n + 1, device=x.device)
+        ml, ll = [model(x, grid[0], **kwargs)], [grid[0]]
+        for step in range(1, order):
+            x, m = update(x, ml, ll, grid[step], step, True)
+            ll.append(grid[step])
+            ml.append(m)
+        for step in range(order, n + 1):
+            x, m = update(x, ml, ll, grid[step], min(order, n + 1 - step), step != n)
+            for i in range(order - 1):
+                ll[i], ml[i] = ll[i + 1], ml[i + 1]
+            ll[-1] = grid[step]
+            if step < n:
                 ml[-1] = m
         return x.clamp(-1.0, 1.0)

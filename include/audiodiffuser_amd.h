@@ -11,6 +11,9 @@
  *                                     :710-768, :470-493), ADPM2Sampler.forward (stochastic_sampler_edm.py:85-100), UniPCSampler.forward (:996-1053)
  *   adf_sampler_run_table          <- VESampler.forward / VPSampler.forward (sampler_edm.py:99-123, :201-227), VSampler.forward / VEulerSampler.forward
  *                                     (src/models/components/sampler_vobj.py:176-194, :92-109): one generic loop over a host table of per-step records
+ *   adf_sampler_run_program        <- sampler_vobj.DPMSampler.forward / UniPCSampler.forward (src/models/components/sampler_vobj.py:389-499, :670-732):
+ *                                     one generic straight-line program over a small register file of state buffers, for linear multistep methods;
+ *                                     with it all ten files under configs/experiment/sc09_inference/ run through this library
  *   the call site all of them sit behind: src/models/diffunet_complex_module.py:86-89
  *   adf_adm_create                 <- UNetModel.__init__ (src/models/backbones/unet2d_oai.py:410-601); adf_net_forward on that handle
  *                                     <- UNetModel.forward (:603-634)
@@ -62,7 +65,9 @@ extern "C" {
  *    because adf_run_counters must not grow within a version.
  *    Added without a bump (new symbols only): adf_sampler_run_table and adf_sampler_table_nfe with their own adf_table_desc / adf_table_step /
  *    adf_table_eval and the three ADF_CLIP_* modes (VESampler, VPSampler, VSampler, VEulerSampler).  No ADF_SAMPLER_* or ADF_PRECOND_* kind is added:
- *    adf_sampler_desc, its kinds and adf_set_preconditioning are as they were. */
+ *    adf_sampler_desc, its kinds and adf_set_preconditioning are as they were.
+ *    Added without a bump (new symbols only): adf_sampler_run_program and adf_sampler_program_nfe with adf_prog_desc / adf_prog_op and the ADF_PROG_*
+ *    constants (VDPMSampler, VUniPCSampler).  adf_table_eval is reused as it is; the table loop and its structs are untouched. */
 #define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
@@ -320,6 +325,47 @@ typedef struct adf_table_desc {
 int adf_sampler_run_table(adf_handle* h, const adf_table_desc* desc, const adf_table_step* steps, const float* noise, const float* injected_noise,
                           int n_injected, float* out, int B, int L, void* stream);
 int adf_sampler_table_nfe(const adf_table_desc* desc, const adf_table_step* steps);
+
+/* The program-driven loop: a sampler with memory (a linear multistep method) whose every branch and scalar depends on the schedule and the constructor
+ * arguments only, handed over as a straight-line host program over ADF_PROG_SLOTS state buffers (fp32 [B][C][L] each).  What runs
+ * sampler_vobj.DPMSampler and sampler_vobj.UniPCSampler (src/models/components/sampler_vobj.py:196-732); audiodiffuser_amd/samplers.py builds their
+ * programs.  Slot 0 starts as x0_scale * noise, every other slot as unwritten.  An op is
+ *     ADF_PROG_EVAL   slot[dst] = clip(c_skip x + c_out net(c_in x, c_noise)), x = slot[src]; `eval` is an adf_table_eval, read as in the table loop
+ *     ADF_PROG_LIN    slot[dst] = sum_{j < n_terms} coef[j] * slot[slot[j]], 1 <= n_terms <= ADF_PROG_TERMS, clamped to [-1, 1] where clamp != 0;
+ *                     one fused pass; dst may be one of the operands
+ * and the sample is slot[result_slot] after the last op.  There are no draws.  A method's history (its earlier model outputs) stays where it was
+ * written: the host renames slots from step to step, nothing is copied.  No evaluation, guided or not, uses a slot as scratch.
+ * In everything else the run behaves as adf_sampler_run_table: labels and guidance from adf_set_condition, the rows taken as given and every c_noise
+ * embedded once at the head of the run (adf_debug_coef_rows returns them), use_graph captures the run once and replays it, with the cache key holding
+ * the descriptor and program bytes and the handle's condition, clipping and preconditioning state; adf_run_counters moves by sampler_runs + 1,
+ * sampler_evals + the number of EVAL ops, graph_replays + 1 when replayed.
+ * Refused before anything is launched, with a message that starts with "adf_sampler_run_program: " and names the argument: a null desc, ops, noise or
+ * out; num_ops <= 0; a non-finite x0_scale; an unknown kind; dst, src, slot[j] or result_slot outside [0, ADF_PROG_SLOTS); a read (src, slot[j],
+ * result_slot) of a slot that neither the start state nor an earlier op has written; an EVAL with dst == src; n_terms outside 1 .. ADF_PROG_TERMS;
+ * the same slot twice in one LIN; a non-finite coef[j] or row entry; an unknown clip; a program without an EVAL.
+ * adf_sampler_program_nfe: host only; the EVAL ops of the program, or -1 for a program the run would refuse for what it holds. */
+#define ADF_PROG_EVAL 0
+#define ADF_PROG_LIN 1
+#define ADF_PROG_SLOTS 8
+#define ADF_PROG_TERMS 5
+typedef struct adf_prog_op {
+    int32_t kind;                 /* ADF_PROG_* */
+    int32_t dst;
+    int32_t src;                  /* EVAL: the slot evaluated */
+    adf_table_eval eval;          /* EVAL */
+    int32_t n_terms;              /* LIN */
+    int32_t slot[ADF_PROG_TERMS]; /* LIN */
+    float coef[ADF_PROG_TERMS];   /* LIN */
+    int32_t clamp;                /* LIN */
+} adf_prog_op;
+typedef struct adf_prog_desc {
+    int32_t num_ops;              /* ops behind `ops` */
+    int32_t result_slot;
+    float x0_scale;               /* slot 0 = x0_scale * noise */
+    int32_t use_graph;
+} adf_prog_desc;
+int adf_sampler_run_program(adf_handle* h, const adf_prog_desc* desc, const adf_prog_op* ops, const float* noise, float* out, int B, int L, void* stream);
+int adf_sampler_program_nfe(const adf_prog_desc* desc, const adf_prog_op* ops);
 
 /* Parity-test support: copy an internal activation of the LAST adf_net_forward/adf_denoise call, converted to
  * fp32 [B][C][L].  Names follow oracle/unet1d.py taps ("to_in", "down0.conv", "down0.block1", "mid.attn", ...). */
