@@ -94,7 +94,7 @@ int create_finish(const char* fn, int dtype, std::unique_ptr<Net> net, adf_handl
     return 0;
 }
 
-// ---- what the two sampler entry points (adf_sampler_run, adf_sampler_run_table) share ------------------------------------------------------------
+// ---- what the three sampler entry points (adf_sampler_run, adf_sampler_run_table, adf_sampler_run_program) share ---------------------------------
 // `floats` floats of injected noise copied into the plan's staging buffer, grown first where it is too small
 static int stage_injected(adf_handle* h, Plan* p, const float* injected_noise, size_t floats, hipStream_t s) {
     if (p->inj_cap < floats) {
@@ -207,6 +207,58 @@ static int run_loop(adf_handle* h, Plan* p, bool use_graph, const std::string& k
     if (hipMemcpyAsync(out, p->out_stage, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "result copy failed");
     ++h->ctr.sampler_runs; ++h->ctr.graph_replays; h->ctr.sampler_evals += n_eval;
     return 0;
+}
+
+// Everything between an entry point's own refusals and the end of its run: the plan and what a run asks of the handle, the buffers an evaluation may
+// need (all_buffers: whatever the handle may be set to; otherwise only what guidance, an unclipped estimate without the fused epilogue or the dynamic
+// threshold needs as it is set now), the noise and the ndraws draws staged, the per-run tables sized -- all before any capture starts -- and run_loop
+// around: upload(coef_all, stream) puts the n_eval rows into Plan::coef_all, they are embedded, body(plan, n, stream, &result) enqueues the rest.
+// `who` prefixes the messages ("" for adf_sampler_run).  draws_refusal, where it is not empty, is reported once the handle and the noise have been
+// seen to, which is where adf_sampler_run has always reported it.  `key` holds the entry point's own bytes; the handle's are appended here.
+template <class Upload, class Body>
+static int run_staged(adf_handle* h, const std::string& who, bool all_buffers, const float* noise, const float* injected_noise, int ndraws,
+                      const std::string& draws_refusal, int n_eval, bool use_graph, std::string key, Upload upload, Body body, float* out, int B, int L,
+                      hipStream_t s) {
+    Plan* p;
+    if (get_plan(h, B, L, s, &p)) return 1;
+    const NetDims& nd = h->net->dims;
+    const long long n = (long long)B * nd.out_channels * L;
+    if (nd.in_channels != nd.out_channels)
+        return fail(h, who.empty() ? "sampler needs in_channels == out_channels" : who + "the handle's network needs in_channels == out_channels");
+    if (h->cdim > 0 && (!h->cond_on || h->cond_B != B))
+        return fail(h, who + "class-conditional network: call adf_set_condition with the labels of this batch first");
+    const bool guided = h->cdim > 0 && h->cond_scale != 1.0f;
+    // unclipped estimate without a mode 2 epilogue: raw pass + combine (denoise_io); the raw kind (ReFlow(for_edm=False)) combines only under guidance
+    const bool combined = h->unclipped() && !h->raw_output() && !h->net->unclipped_epilogue;
+    const bool dyn = h->dyn_q > 0.0f;
+    if ((all_buffers || guided || combined || dyn) && ensure_cfg_buffers(h, p)) return 1;
+    if (dyn && ensure_dyn_scale(h, p, who)) return 1;
+    if (hipMemcpyAsync(p->noise_stage, noise, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, who + "noise copy failed");
+    if (!draws_refusal.empty()) return fail(h, draws_refusal);
+    if (ndraws > 0 && stage_injected(h, p, injected_noise, (size_t)ndraws * n, s)) return 1;
+    if (reserve_eval_tables(h, p, n_eval)) return 1;
+    // head of the loop (inside the captured graph when there is one): coefficients, sigma embeddings and FiLM projections of all evaluations in
+    // three launches
+    auto enqueue = [&](hipStream_t st, float** result) -> int {
+        if (n_eval > 0) {
+            if (const char* e = upload(p->coef_all, st)) return fail(h, e);
+            if (embed_eval_tables(h, p, n_eval, st)) return 1;
+        }
+        return body(p, n, st, result);
+    };
+    if (use_graph) append_handle_key(h, &key);
+    return run_loop(h, p, use_graph, key, enqueue, out, n, n_eval, s);
+}
+
+// One run of a lowered op list (adf_sampler.hip): the rows are uploaded as the list gives them instead of being derived from sigmas, and an evaluation
+// may end in any ADF_CLIP_* mode, so every buffer is allocated.
+static int run_op_list(adf_handle* h, const std::string& who, const OpList& l, const float* noise, const float* injected_noise, int ndraws, bool use_graph,
+                       const std::string& key, float* out, int B, int L, hipStream_t s) {
+    const std::vector<float> rows = op_rows(l);
+    const int n_eval = (int)(rows.size() / 4);
+    return run_staged(h, who, true, noise, injected_noise, ndraws, "", n_eval, use_graph, key,
+                      [&](float* coef_all, hipStream_t st) { return launch_coef_rows(rows.data(), n_eval, coef_all, st); },
+                      [&](Plan* p, long long n, hipStream_t st, float** result) { return run_ops(h, p, l, n, st, result); }, out, B, L, s);
 }
 
 }  // namespace adf_api
@@ -436,67 +488,38 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
     ADF_ON_DEVICE(h);
     hipStream_t s = (hipStream_t)stream;
     if (!desc || !sigmas_host || n_sigmas < 1) return fail(h, "adf_sampler_run: bad arguments");
-    Plan* p;
-    if (get_plan(h, B, L, s, &p)) return 1;
-    const NetDims& nd = h->net->dims;
-    const long long n = (long long)B * nd.out_channels * L;
-    if (nd.in_channels != nd.out_channels) return fail(h, "sampler needs in_channels == out_channels");
-    if (h->cdim > 0) {
-        if (!h->cond_on || h->cond_B != B) return fail(h, "class-conditional network: call adf_set_condition with the labels of this batch first");
-        if (h->cond_scale != 1.0f && ensure_cfg_buffers(h, p)) return 1;
-    }
-    // unclipped estimate without a mode 2 epilogue: raw pass + combine (denoise_io); the raw kind (ReFlow(for_edm=False)) combines only under guidance (above)
-    if (h->unclipped() && !h->raw_output() && !h->net->unclipped_epilogue && ensure_cfg_buffers(h, p)) return 1;
-    if (h->dyn_q > 0.0f) {                               // buffers of the dynamic threshold: allocated before any capture starts
-        if (ensure_cfg_buffers(h, p)) return 1;
-        if (!p->dyn_scale) {
-            p->dyn_scale = (float*)dalloc(h, (size_t)B * 4, p);
-            if (!p->dyn_scale) return fail(h, "device allocation failed for the dynamic-threshold scales");
-        }
-    }
-    if (hipMemcpyAsync(p->noise_stage, noise, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "noise copy failed");
     const int ndraws = sampler_draws(*desc, sigmas_host, n_sigmas);
+    std::string draws_refusal;
     if (ndraws > 0 && !injected_noise)
-        return fail(h, desc->kind == ADF_SAMPLER_ADPM2 ? "ADPM2Sampler needs injected_noise (one pre-drawn randn_like tensor per step)"
-                       : desc->kind == ADF_SAMPLER_ADPMPP2S ? "ADPMPP2SSampler needs injected_noise (one pre-drawn randn_like tensor per step with sigma_next > 0)"
-                                                            : "a sampler with s_churn > 0 needs injected_noise (pre-drawn randn_like tensors)");
-    if (ndraws > 0) {
-        const size_t need = (size_t)ndraws * n;
-        // the ABI carries the number of [B][C][L] draws behind the pointer: a short buffer is an error, not an over-read
-        if (n_injected < ndraws)
-            return fail(h, "injected_noise holds " + std::to_string(n_injected) + " draws of [B][C][L], this sampler consumes " + std::to_string(ndraws));
-        if (stage_injected(h, p, injected_noise, need, s)) return 1;
-    }
-    // the sigma of every denoiser evaluation of this run (host logic only), then the buffers of the per-run table -- sized
-    // before any capture starts
+        draws_refusal = desc->kind == ADF_SAMPLER_ADPM2 ? "ADPM2Sampler needs injected_noise (one pre-drawn randn_like tensor per step)"
+                        : desc->kind == ADF_SAMPLER_ADPMPP2S ? "ADPMPP2SSampler needs injected_noise (one pre-drawn randn_like tensor per step with sigma_next > 0)"
+                                                             : "a sampler with s_churn > 0 needs injected_noise (pre-drawn randn_like tensors)";
+    else if (ndraws > 0 && n_injected < ndraws)      // the ABI carries the number of [B][C][L] draws behind the pointer: a short buffer is an error, not an over-read
+        draws_refusal = "injected_noise holds " + std::to_string(n_injected) + " draws of [B][C][L], this sampler consumes " + std::to_string(ndraws);
+    // the sigma of every denoiser evaluation of this run (host logic only)
     std::vector<float> eval_sigmas;
     if (count_sampler(desc, sigmas_host, n_sigmas, &eval_sigmas) < 0) eval_sigmas.clear();     // a schedule the sampler rejects: the real pass below reports why
     const int n_eval = (int)eval_sigmas.size();
-    if (reserve_eval_tables(h, p, n_eval)) return 1;
-    // head of the loop (inside the captured graph when there is one): coefficients, sigma embeddings and FiLM projections of all
-    // evaluations in three launches
-    SamplerCtx c{h, p, desc, sigmas_host, n_sigmas, s, n};
-    c.precomputed = n_eval > 0;
-    auto enqueue = [&](hipStream_t st, float** result) -> int {
-        c.s = st;
-        if (n_eval > 0) {
-            if (const char* e = launch_edm_coef_list(eval_sigmas.data(), n_eval, h->precond_for(desc->sigma_data), p->coef_all, st)) return fail(h, e);
-            if (embed_eval_tables(h, p, n_eval, st)) return 1;
-        }
-        return run_sampler(c, result);
-    };
     std::string key;
     if (desc->use_graph) {
         key.assign((const char*)desc, sizeof(*desc));
         key.append((const char*)sigmas_host, (size_t)n_sigmas * 4);
         key.push_back(injected_noise ? 'i' : 'n');
-        append_handle_key(h, &key);
     }
-    return run_loop(h, p, desc->use_graph != 0, key, enqueue, out, n, n_eval, s);
+    return run_staged(h, "", false, noise, injected_noise, ndraws, draws_refusal, n_eval, desc->use_graph != 0, key,
+                      [&](float* coef_all, hipStream_t st) {
+                          return launch_edm_coef_list(eval_sigmas.data(), n_eval, h->precond_for(desc->sigma_data), coef_all, st);
+                      },
+                      [&](Plan* p, long long n, hipStream_t st, float** result) {
+                          SamplerCtx c{h, p, desc, sigmas_host, n_sigmas, st, n};
+                          c.precomputed = n_eval > 0;
+                          return run_sampler(c, result);
+                      },
+                      out, B, L, s);
 }
 
-// The table-driven loop (adf_sampler.hip: table_refusal, table_rows, run_table).  The same staging, per-run evaluation tables, capture cache and
-// counters as adf_sampler_run; the rows are uploaded as the table gives them instead of being derived from sigmas.
+// The two public forms of the op loop (adf_sampler.hip).  The same staging, per-run evaluation tables, capture cache and counters as adf_sampler_run.
+// The table form: one record per step, lowered to ops; a record may read a draw.
 int adf_sampler_run_table(adf_handle* h, const adf_table_desc* desc, const adf_table_step* steps, const float* noise, const float* injected_noise,
                           int n_injected, float* out, int B, int L, void* stream) {
     if (!h) return 1;
@@ -515,49 +538,23 @@ int adf_sampler_run_table(adf_handle* h, const adf_table_desc* desc, const adf_t
                                std::to_string(n_injected) + " draws of injected_noise (n_injected)");
         ndraws = std::max(ndraws, steps[i].draw + 1);
     }
-    Plan* p;
-    if (get_plan(h, B, L, s, &p)) return 1;
-    const NetDims& nd = h->net->dims;
-    const long long n = (long long)B * nd.out_channels * L;
-    if (nd.in_channels != nd.out_channels) return fail(h, "adf_sampler_run_table: the handle's network needs in_channels == out_channels");
-    if (h->cdim > 0 && (!h->cond_on || h->cond_B != B))
-        return fail(h, "adf_sampler_run_table: class-conditional network: call adf_set_condition with the labels of this batch first");
-    // whatever an evaluation of the table may need (guidance, an unclipped estimate without the fused epilogue, the dynamic threshold): before any capture
-    if (ensure_cfg_buffers(h, p)) return 1;
-    if (h->dyn_q > 0.0f && !p->dyn_scale) {
-        p->dyn_scale = (float*)dalloc(h, (size_t)B * 4, p);
-        if (!p->dyn_scale) return fail(h, "adf_sampler_run_table: device allocation failed for the dynamic-threshold scales");
-    }
-    if (hipMemcpyAsync(p->noise_stage, noise, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "adf_sampler_run_table: noise copy failed");
-    if (ndraws > 0 && stage_injected(h, p, injected_noise, (size_t)ndraws * n, s)) return 1;
-    std::vector<float> rows;
-    table_rows(desc, steps, &rows);
-    const int n_eval = (int)(rows.size() / 4);
-    if (reserve_eval_tables(h, p, n_eval)) return 1;
-    auto enqueue = [&](hipStream_t st, float** result) -> int {
-        if (const char* e = launch_coef_rows(rows.data(), n_eval, p->coef_all, st)) return fail(h, e);
-        if (embed_eval_tables(h, p, n_eval, st)) return 1;
-        return run_table(h, p, desc, steps, n, st, result);
-    };
     std::string key;
     if (desc->use_graph) {
         key.assign("table");                                  // no adf_sampler_desc starts with these bytes (its first field is a kind below 11)
         key.append((const char*)desc, sizeof(*desc));
         key.append((const char*)steps, (size_t)desc->num_steps * sizeof(*steps));
-        append_handle_key(h, &key);
     }
-    return run_loop(h, p, desc->use_graph != 0, key, enqueue, out, n, n_eval, s);
+    return run_op_list(h, "adf_sampler_run_table: ", lower_table(desc, steps), noise, injected_noise, ndraws, desc->use_graph != 0, key, out, B, L, s);
 }
 
 int adf_sampler_table_nfe(const adf_table_desc* desc, const adf_table_step* steps) {
     if (!table_refusal(desc, steps).empty()) return -1;
-    std::vector<float> rows;
-    table_rows(desc, steps, &rows);
-    return (int)(rows.size() / 4);
+    int nfe = 0;                                              // counted off the table: nobody has checked its draws, so it is not lowered
+    for (int i = 0; i < desc->num_steps; ++i) nfe += steps[i].second ? 2 : 1;
+    return nfe;
 }
 
-// The program-driven loop (adf_sampler.hip: program_refusal, program_rows, run_program): adf_sampler_run_table's staging, per-run evaluation tables,
-// capture cache and counters around a straight-line program over the plan's state buffers.  It reads no draws.
+// The program form: a straight-line program over the plan's state buffers, which is the op list as it stands.  It reads no draws.
 int adf_sampler_run_program(adf_handle* h, const adf_prog_desc* desc, const adf_prog_op* ops, const float* noise, float* out, int B, int L, void* stream) {
     if (!h) return 1;
     ADF_ON_DEVICE(h);
@@ -566,44 +563,18 @@ int adf_sampler_run_program(adf_handle* h, const adf_prog_desc* desc, const adf_
     if (!why.empty()) return fail(h, "adf_sampler_run_program: " + why);
     if (!noise) return fail(h, "adf_sampler_run_program: noise is null");
     if (!out) return fail(h, "adf_sampler_run_program: out is null");
-    Plan* p;
-    if (get_plan(h, B, L, s, &p)) return 1;
-    const NetDims& nd = h->net->dims;
-    const long long n = (long long)B * nd.out_channels * L;
-    if (nd.in_channels != nd.out_channels) return fail(h, "adf_sampler_run_program: the handle's network needs in_channels == out_channels");
-    if (h->cdim > 0 && (!h->cond_on || h->cond_B != B))
-        return fail(h, "adf_sampler_run_program: class-conditional network: call adf_set_condition with the labels of this batch first");
-    // whatever an evaluation of the program may need (guidance, an unclipped estimate without the fused epilogue, the dynamic threshold): before any capture
-    if (ensure_cfg_buffers(h, p)) return 1;
-    if (h->dyn_q > 0.0f && !p->dyn_scale) {
-        p->dyn_scale = (float*)dalloc(h, (size_t)B * 4, p);
-        if (!p->dyn_scale) return fail(h, "adf_sampler_run_program: device allocation failed for the dynamic-threshold scales");
-    }
-    if (hipMemcpyAsync(p->noise_stage, noise, (size_t)n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return fail(h, "adf_sampler_run_program: noise copy failed");
-    std::vector<float> rows;
-    program_rows(desc, ops, &rows);
-    const int n_eval = (int)(rows.size() / 4);
-    if (reserve_eval_tables(h, p, n_eval)) return 1;
-    auto enqueue = [&](hipStream_t st, float** result) -> int {
-        if (const char* e = launch_coef_rows(rows.data(), n_eval, p->coef_all, st)) return fail(h, e);
-        if (embed_eval_tables(h, p, n_eval, st)) return 1;
-        return run_program(h, p, desc, ops, n, st, result);
-    };
     std::string key;
     if (desc->use_graph) {
         key.assign("program");                                // no other key starts with these bytes ("table", or a sampler kind below 11)
         key.append((const char*)desc, sizeof(*desc));
         key.append((const char*)ops, (size_t)desc->num_ops * sizeof(*ops));
-        append_handle_key(h, &key);
     }
-    return run_loop(h, p, desc->use_graph != 0, key, enqueue, out, n, n_eval, s);
+    return run_op_list(h, "adf_sampler_run_program: ", lower_program(desc, ops), noise, nullptr, 0, desc->use_graph != 0, key, out, B, L, s);
 }
 
 int adf_sampler_program_nfe(const adf_prog_desc* desc, const adf_prog_op* ops) {
     if (!program_refusal(desc, ops).empty()) return -1;
-    std::vector<float> rows;
-    program_rows(desc, ops, &rows);
-    return (int)(rows.size() / 4);
+    return (int)(op_rows(lower_program(desc, ops)).size() / 4);
 }
 
 int adf_abi_version(void) { return ADF_ABI_VERSION; }

@@ -7,7 +7,8 @@
 //   adf_net_unet2d.hip     Unet2dNet: Imagen-style UNet2dBase (unet2d.py:622-972), exact fp32: adf_unet2d_create, registry, walk
 //   adf_walk2d.h           what the two 2-D walks share: fine GroupNorm statistics, the conv launch, the conditioning prologue
 //   adf_sampler.hip        denoise wrappers; the eleven sampler drivers (sampler_edm.py, stochastic_sampler_edm.py, sampler_rf.py), written on SamplerCtx's
-//                          members (below), which own the split between the counting pass and the real pass; count_sampler, sampler_draws
+//                          members (below), which own the split between the counting pass and the real pass; count_sampler, sampler_draws; the op
+//                          loop behind the table form and the program form (run_ops, at the end of this header)
 //   adf_bench_replay.hip   adf_bench_* instrumentation
 // A handle owns one Net (below).  This header, adf_api.hip and adf_sampler.hip know a network only through that interface.
 #pragma once
@@ -342,6 +343,17 @@ inline EvalClip handle_clip(const adf_handle* h) {
 }
 int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s);                        // ends as the handle is set (handle_clip)
 int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, const EvalClip& ec, hipStream_t s);
+// Plan::dyn_scale, allocated where it is missing (outside graph capture, like ensure_cfg_buffers); `who` prefixes the message
+int ensure_dyn_scale(adf_handle* h, Plan* p, const std::string& who = "");
+// Evaluation k of a sampler run on x: it reads row k of Plan::coef_all and of temb_all / film_all, filled and embedded at the head of the run
+inline FwdIO row_io(const adf_handle* h, const Plan* p, int k, const float* x) {
+    FwdIO io;
+    io.x = x; io.t = p->coef_all + (size_t)k * 4 + 1; io.t_stride = 4; io.nb = 1;
+    io.coef = p->coef_all + (size_t)k * 4; io.coef_bstride = 0; io.x_noisy = x;
+    if (h->per_sample_film()) io.temb_pre = p->temb_all + (size_t)k * h->net->dims.temb;
+    else io.film_pre = p->film_all + (size_t)k * h->film_total;
+    return io;
+}
 int denoise_scalar(adf_handle* h, Plan* p, const float* x, float sigma, float sigma_data, float* out, hipStream_t s);
 // one evaluation with a sigma per sample (sigmas_dev [B] on the device): what adf_denoise enqueues, and the middle of adf_diffusion_loss
 int denoise_rows(adf_handle* h, Plan* p, const float* x, const float* sigmas_dev, float sigma_data, float* out, hipStream_t s);
@@ -374,14 +386,7 @@ struct SamplerCtx {
     int den(const float* x, float sigma, float* out) {
         const int k = nfe++;
         if (count_only) { if (collect) collect->push_back(sigma); return 0; }
-        if (precomputed) {
-            FwdIO io;
-            io.x = x; io.t = p->coef_all + (size_t)k * 4 + 1; io.t_stride = 4; io.nb = 1;
-            io.coef = p->coef_all + (size_t)k * 4; io.coef_bstride = 0; io.x_noisy = x;
-            if (h->per_sample_film()) io.temb_pre = p->temb_all + (size_t)k * h->net->dims.temb;
-            else io.film_pre = p->film_all + (size_t)k * h->film_total;
-            return denoise_io(h, p, io, out, s);
-        }
+        if (precomputed) return denoise_io(h, p, row_io(h, p, k, x), out, s);
         return denoise_scalar(h, p, x, sigma, d->sigma_data, out, s);
     }
     // DPMSampler.model_fn (sampler_edm.py:692-708): the denoised estimate, or with eps_pred the noise prediction (x - D) / sigma
@@ -397,15 +402,17 @@ int count_sampler(const adf_sampler_desc* d, const float* sig, int nsig, std::ve
 // [B][C][L] draws of the injected noise the driver reads on this schedule (0: the sampler runs without injected_noise)
 int sampler_draws(const adf_sampler_desc& d, const float* sig, int nsig);
 
-// The table-driven loop (adf_sampler_run_table, adf_sampler.hip).  table_refusal: why the table cannot run ("" when it can; host only);
-// table_rows: the (c_in, c_noise, c_skip, c_out) of its evaluations in order; run_table enqueues the loop on the rows already in Plan::coef_all.
+// The op loop (adf_sampler.hip) behind the two public forms, adf_sampler_run_table and adf_sampler_run_program.  Each form has its refusal (why it cannot
+// run, in the caller's argument names; "" when it can; host only) and its lowering to one OpList; the rows and the NFE of a run are read off the list,
+// and run_ops enqueues it on the rows already in Plan::coef_all.  An op of the list is the public program op over a wider slot space: 0 .. 9 are
+// Plan::sb[k], the range above them names the draws of Plan::inj_stage, which only a lowered table reads (program_refusal admits no such slot).
+struct OpList { std::vector<adf_prog_op> ops; float x0_scale = 1.0f; int result_slot = 0; };
 bool table_reads_eps(const adf_table_step& r);
 std::string table_refusal(const adf_table_desc* d, const adf_table_step* st);
-void table_rows(const adf_table_desc* d, const adf_table_step* st, std::vector<float>* rows);
-int run_table(adf_handle* h, Plan* p, const adf_table_desc* d, const adf_table_step* st, long long n, hipStream_t s, float** result);
-// The program-driven loop (adf_sampler_run_program, adf_sampler.hip), in the same three parts.
 std::string program_refusal(const adf_prog_desc* d, const adf_prog_op* ops);
-void program_rows(const adf_prog_desc* d, const adf_prog_op* ops, std::vector<float>* rows);
-int run_program(adf_handle* h, Plan* p, const adf_prog_desc* d, const adf_prog_op* ops, long long n, hipStream_t s, float** result);
+OpList lower_table(const adf_table_desc* d, const adf_table_step* st);
+OpList lower_program(const adf_prog_desc* d, const adf_prog_op* ops);
+std::vector<float> op_rows(const OpList& l);      // the (c_in, c_noise, c_skip, c_out) of the list's evaluations, in order
+int run_ops(adf_handle* h, Plan* p, const OpList& l, long long n, hipStream_t s, float** result);
 
 }  // namespace adf_api

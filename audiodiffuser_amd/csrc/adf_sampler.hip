@@ -31,6 +31,13 @@ int ensure_cfg_buffers(adf_handle* h, Plan* p) {
     return 0;
 }
 
+int ensure_dyn_scale(adf_handle* h, Plan* p, const std::string& who) {
+    if (p->dyn_scale) return 0;
+    p->dyn_scale = (float*)dalloc(h, (size_t)p->B * 4, p);
+    if (!p->dyn_scale) return fail(h, who + "device allocation failed for the dynamic-threshold scales");
+    return 0;
+}
+
 // One denoiser evaluation.  io carries x / t / coef (preconditioning scalars already in p->coef); with classifier-free
 // guidance the network runs twice (labels, null labels) in raw mode and cfg_combine applies guidance + preconditioning.
 // Dynamic thresholding (EluDiffusion(dynamic_threshold = q), components/utils.py:23-33): the estimate leaves the combine kernel unclipped and is
@@ -38,7 +45,7 @@ int ensure_cfg_buffers(adf_handle* h, Plan* p) {
 // nets, and under guidance, it is the raw pass + cfg_combine without the clamp.
 int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s) { return denoise_io(h, p, io, out, handle_clip(h), s); }
 
-// The same with the end of the evaluation given by the caller (the table-driven loop names it per evaluation; every other caller takes the handle's).
+// The same with the end of the evaluation given by the caller (the op loop names it per evaluation; every other caller takes the handle's).
 int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, const EvalClip& ec, hipStream_t s) {
     const bool cfg = h->cdim > 0 && h->cond_on && h->cond_scale != 1.0f;
     const bool noclip = ec.noclip, raw = ec.raw, dyn = ec.dyn;
@@ -51,11 +58,7 @@ int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, const EvalClip& ec,
     }
     const long long per_sample = (long long)h->net->dims.out_channels * p->L;
     const size_t wave = (size_t)p->B * per_sample;
-    if (ensure_cfg_buffers(h, p)) return 1;
-    if (dyn && !p->dyn_scale) {
-        p->dyn_scale = (float*)dalloc(h, (size_t)p->B * 4, p);
-        if (!p->dyn_scale) return fail(h, "device allocation failed for the dynamic-threshold scales");
-    }
+    if (ensure_cfg_buffers(h, p) || (dyn && ensure_dyn_scale(h, p))) return 1;
     io.mode = 0;                                     // raw network output; c_in is still applied by to_in
     io.out = p->cfg_c;
     if (cond_rows(h, p->B, false, io) || forward(h, p, io, s)) return 1;
@@ -684,10 +687,28 @@ int sampler_draws(const adf_sampler_desc& d, const float* sig, int nsig) {
     }
 }
 
-// ---- the table-driven loop (adf_sampler_run_table; the step form is in the header) --------------------------------------------------------------
+// ---- the op loop (adf_sampler_run_table, adf_sampler_run_program; the two public forms are in the header) ----------------------------------------
 // VESampler / VPSampler (sampler_edm.py:31-227) and VSampler / VEulerSampler (sampler_vobj.py:31-194): the host resolves every branch and scalar of
-// those loops into one record per step (audiodiffuser_amd/samplers.py), so there is one driver and it knows none of them.
+// those loops into one record per step (audiodiffuser_amd/samplers.py).  VDPMSampler / VUniPCSampler (sampler_vobj.py:196-732) are linear multistep
+// methods: a step reads the state and up to three earlier model outputs, the UniPC corrector the one just computed as well, so the host resolves a run
+// into a straight-line program over ADF_PROG_SLOTS state buffers; history rotation is slot renaming there, so nothing is copied.  A table is a program
+// of a fixed shape that also reads draws: both forms are lowered to one op list (lower_table, lower_program) and one driver, run_ops, runs it and knows
+// none of the six samplers.  No evaluation touches Plan::sb (the guided one writes Plan::cfg_c / cfg_n), so the register file is Plan::sb.
+constexpr int kStateSlots = 10;           // slots below: Plan::sb[slot]; from here on: draw (slot - kStateSlots) of Plan::inj_stage
+static_assert(kStateSlots == sizeof(Plan::sb) / sizeof(float*), "the register file is Plan::sb");
+static_assert(ADF_PROG_SLOTS <= kStateSlots, "a slot of the public program form never reaches the draw range");
+static_assert(ADF_PROG_TERMS == 5, "launch_lin takes 1 to 5 operands");
+
 bool table_reads_eps(const adf_table_step& r) { return r.a1 != 0.0f || r.b2 != 0.0f; }
+
+static bool all_finite(std::initializer_list<float> v) { for (float f : v) if (!std::isfinite(f)) return false; return true; }
+
+// what is wrong with the row or the clip of an evaluation, as the end of a message that starts with the evaluation's name, or nullptr
+static const char* eval_refusal(const adf_table_eval& e) {
+    if (!all_finite({e.c_in, e.c_noise, e.c_skip, e.c_out})) return " holds a non-finite row entry";
+    if (e.clip != ADF_CLIP_NONE && e.clip != ADF_CLIP_CONFIGURED && e.clip != ADF_CLIP_UNIT) return ".clip is no ADF_CLIP_* mode";
+    return nullptr;
+}
 
 // Why the table cannot run, naming the argument, or "" (host only; the draws are the entry point's to check).
 std::string table_refusal(const adf_table_desc* d, const adf_table_step* st) {
@@ -695,17 +716,11 @@ std::string table_refusal(const adf_table_desc* d, const adf_table_step* st) {
     if (!st) return "steps is null";
     if (d->num_steps <= 0) return "desc.num_steps = " + std::to_string(d->num_steps) + " must be positive";
     if (!std::isfinite(d->x0_scale)) return "desc.x0_scale is not finite";
-    auto all_finite = [](std::initializer_list<float> v) { for (float f : v) if (!std::isfinite(f)) return false; return true; };
-    auto bad_eval = [&](const adf_table_eval& e) -> const char* {
-        if (!all_finite({e.c_in, e.c_noise, e.c_skip, e.c_out})) return " holds a non-finite row entry";
-        if (e.clip != ADF_CLIP_NONE && e.clip != ADF_CLIP_CONFIGURED && e.clip != ADF_CLIP_UNIT) return ".clip is no ADF_CLIP_* mode";
-        return nullptr;
-    };
     for (int i = 0; i < d->num_steps; ++i) {
         const adf_table_step& r = st[i];
         const std::string at = "steps[" + std::to_string(i) + "]";
         if (!all_finite({r.a0, r.a1, r.b0, r.b1, r.b2})) return at + " holds a non-finite coefficient (a0, a1, b0, b1, b2)";
-        if (const char* e = bad_eval(r.eval1)) return at + ".eval1" + e;
+        if (const char* e = eval_refusal(r.eval1)) return at + ".eval1" + e;
         if (r.a0 == 0.0f && r.a1 == 0.0f) return at + ": a0 == a1 == 0 leaves no x_hat to evaluate";
         const bool no_xe = r.b0 == 0.0f && r.b1 == 0.0f && r.b2 == 0.0f;
         if (!r.second) {
@@ -714,73 +729,11 @@ std::string table_refusal(const adf_table_desc* d, const adf_table_step* st) {
         }
         if (no_xe) return at + ".second asks for D2 without x_e (b0 == b1 == b2 == 0)";
         if (!all_finite({r.c0, r.c1, r.c2, r.c3})) return at + " holds a non-finite coefficient (c0 .. c3)";
-        if (const char* e = bad_eval(r.eval2)) return at + ".eval2" + e;
+        if (const char* e = eval_refusal(r.eval2)) return at + ".eval2" + e;
         if (r.c0 == 0.0f && r.c1 == 0.0f && r.c2 == 0.0f && r.c3 == 0.0f) return at + ": c0 == c1 == c2 == c3 == 0 leaves no next state";
     }
     return "";
 }
-
-// the rows of every evaluation of the table, in order (four floats each)
-void table_rows(const adf_table_desc* d, const adf_table_step* st, std::vector<float>* rows) {
-    rows->clear();
-    for (int i = 0; i < d->num_steps; ++i)
-        for (const adf_table_eval* e : {&st[i].eval1, st[i].second ? &st[i].eval2 : nullptr})
-            if (e) rows->insert(rows->end(), {e->c_in, e->c_noise, e->c_skip, e->c_out});
-}
-
-// Evaluation k of the run (row k of Plan::coef_all, embedded at the head of the run) on x, ending as `e.clip` says.
-static int table_eval(adf_handle* h, Plan* p, int k, const adf_table_eval& e, const float* x, float* out, hipStream_t s) {
-    FwdIO io;
-    io.x = x; io.t = p->coef_all + (size_t)k * 4 + 1; io.t_stride = 4; io.nb = 1;
-    io.coef = p->coef_all + (size_t)k * 4; io.coef_bstride = 0; io.x_noisy = x;
-    if (h->per_sample_film()) io.temb_pre = p->temb_all + (size_t)k * h->net->dims.temb;
-    else io.film_pre = p->film_all + (size_t)k * h->film_total;
-    EvalClip ec;
-    ec.noclip = e.clip == ADF_CLIP_NONE || (e.clip == ADF_CLIP_CONFIGURED && h->unclipped());
-    ec.dyn = e.clip == ADF_CLIP_CONFIGURED && h->dyn_q > 0.0f && !ec.noclip;
-    ec.raw = ec.noclip && e.c_skip == 0.0f && e.c_out == 1.0f;      // the estimate is the network output: written straight into `out`
-    return denoise_io(h, p, io, out, ec, s);
-}
-
-// One update: out = sum of the operands whose coefficient is not zero (table_refusal has seen to it that one is left).
-static int table_lin(adf_handle* h, float* out, std::initializer_list<std::pair<const float*, float>> ops, int clampit, long long n, hipStream_t s) {
-    LinTerms t;
-    memset(&t, 0, sizeof(t));
-    for (const auto& op : ops)
-        if (op.second != 0.0f) { t.p[t.n] = op.first; t.k[t.n] = op.second; ++t.n; }
-    if (const char* e = launch_lin(out, t, clampit, n, s)) return fail(h, e);
-    return 0;
-}
-
-int run_table(adf_handle* h, Plan* p, const adf_table_desc* d, const adf_table_step* st, long long n, hipStream_t s, float** result) {
-    float *X = p->sb[0], *D1 = p->sb[1], *XE = p->sb[2], *D2 = p->sb[3];
-    if (const char* e = launch_scale(X, p->noise_stage, d->x0_scale, n, s)) return fail(h, e);
-    int k = 0;
-    for (int i = 0; i < d->num_steps; ++i) {
-        const adf_table_step& r = st[i];
-        const float* eps = table_reads_eps(r) ? p->inj_stage + (size_t)r.draw * n : nullptr;
-        const int clampit = d->final_clamp && i + 1 == d->num_steps;       // the closing clamp rides in the last update
-        if (!(r.a0 == 1.0f && r.a1 == 0.0f) && table_lin(h, X, {{X, r.a0}, {eps, r.a1}}, 0, n, s)) return 1;     // X holds x_hat from here on
-        if (table_eval(h, p, k++, r.eval1, X, D1, s)) return 1;
-        if (!r.second) {
-            if (table_lin(h, X, {{X, r.b0}, {D1, r.b1}, {eps, r.b2}}, clampit, n, s)) return 1;
-            continue;
-        }
-        if (table_lin(h, XE, {{X, r.b0}, {D1, r.b1}, {eps, r.b2}}, 0, n, s)) return 1;
-        if (table_eval(h, p, k++, r.eval2, XE, D2, s)) return 1;
-        if (table_lin(h, X, {{X, r.c0}, {D1, r.c1}, {XE, r.c2}, {D2, r.c3}}, clampit, n, s)) return 1;
-    }
-    *result = X;
-    return 0;
-}
-
-// ---- the program-driven loop (adf_sampler_run_program; the op form is in the header) -------------------------------------------------------------
-// VDPMSampler / VUniPCSampler (sampler_vobj.py:196-732) are linear multistep methods: a step reads the state and up to three earlier model outputs, the
-// UniPC corrector the one just computed as well.  The host resolves a run into a straight-line program over ADF_PROG_SLOTS state buffers
-// (audiodiffuser_amd/samplers.py); history rotation is slot renaming there, so this driver copies nothing and knows neither method.  No evaluation
-// touches Plan::sb (the guided one writes Plan::cfg_c / cfg_n), so the register file is sb[0 .. ADF_PROG_SLOTS).
-static_assert(ADF_PROG_SLOTS <= 10, "the register file is Plan::sb");
-static_assert(ADF_PROG_TERMS == 5, "launch_lin takes 1 to 5 operands");
 
 // Why the program cannot run, naming the argument, or "" (host only).
 std::string program_refusal(const adf_prog_desc* d, const adf_prog_op* ops) {
@@ -800,10 +753,7 @@ std::string program_refusal(const adf_prog_desc* d, const adf_prog_op* ops) {
             if (!slot_ok(o.src)) return at + ".src = " + std::to_string(o.src) + " is outside the " + std::to_string(ADF_PROG_SLOTS) + " slots";
             if (!written[o.src]) return at + ".src reads slot " + std::to_string(o.src) + ", which nothing has written";
             if (o.dst == o.src) return at + ": dst == src (an evaluation cannot overwrite its input)";
-            const adf_table_eval& e = o.eval;
-            if (!std::isfinite(e.c_in) || !std::isfinite(e.c_noise) || !std::isfinite(e.c_skip) || !std::isfinite(e.c_out))
-                return at + ".eval holds a non-finite row entry";
-            if (e.clip != ADF_CLIP_NONE && e.clip != ADF_CLIP_CONFIGURED && e.clip != ADF_CLIP_UNIT) return at + ".eval.clip is no ADF_CLIP_* mode";
+            if (const char* e = eval_refusal(o.eval)) return at + ".eval" + e;
             ++n_eval;
         } else {
             if (o.n_terms < 1 || o.n_terms > ADF_PROG_TERMS)
@@ -825,29 +775,83 @@ std::string program_refusal(const adf_prog_desc* d, const adf_prog_op* ops) {
     return "";
 }
 
-// the rows of every evaluation of the program, in order (four floats each)
-void program_rows(const adf_prog_desc* d, const adf_prog_op* ops, std::vector<float>* rows) {
-    rows->clear();
-    for (int i = 0; i < d->num_ops; ++i)
-        if (ops[i].kind == ADF_PROG_EVAL) rows->insert(rows->end(), {ops[i].eval.c_in, ops[i].eval.c_noise, ops[i].eval.c_skip, ops[i].eval.c_out});
+// The table as ops (the step form is in the header): X, D1, x_e and D2 live in slots 0 to 3 and X holds x_hat after the a-update, which a0 == 1, a1 == 0
+// leaves out.  An operand whose coefficient is zero is dropped (table_refusal has seen to it that one is left); the closing clamp rides in the last update.
+OpList lower_table(const adf_table_desc* d, const adf_table_step* st) {
+    enum { X, D1, XE, D2 };
+    OpList l;
+    l.x0_scale = d->x0_scale; l.result_slot = X;
+    auto eval = [&l](int dst, int src, const adf_table_eval& e) {
+        adf_prog_op o{};
+        o.kind = ADF_PROG_EVAL; o.dst = dst; o.src = src; o.eval = e;
+        l.ops.push_back(o);
+    };
+    auto lin = [&l](int dst, std::initializer_list<std::pair<int, float>> terms, int clampit) {
+        adf_prog_op o{};
+        o.kind = ADF_PROG_LIN; o.dst = dst; o.clamp = clampit;
+        for (const auto& t : terms)
+            if (t.second != 0.0f) { o.slot[o.n_terms] = t.first; o.coef[o.n_terms] = t.second; ++o.n_terms; }
+        l.ops.push_back(o);
+    };
+    for (int i = 0; i < d->num_steps; ++i) {
+        const adf_table_step& r = st[i];
+        const int eps = table_reads_eps(r) ? kStateSlots + r.draw : -1;      // (the entry point has checked the draw of a record that reads one)
+        const int clampit = d->final_clamp && i + 1 == d->num_steps;
+        if (!(r.a0 == 1.0f && r.a1 == 0.0f)) lin(X, {{X, r.a0}, {eps, r.a1}}, 0);
+        eval(D1, X, r.eval1);
+        if (!r.second) {
+            lin(X, {{X, r.b0}, {D1, r.b1}, {eps, r.b2}}, clampit);
+            continue;
+        }
+        lin(XE, {{X, r.b0}, {D1, r.b1}, {eps, r.b2}}, 0);
+        eval(D2, XE, r.eval2);
+        lin(X, {{X, r.c0}, {D1, r.c1}, {XE, r.c2}, {D2, r.c3}}, clampit);
+    }
+    return l;
 }
 
-int run_program(adf_handle* h, Plan* p, const adf_prog_desc* d, const adf_prog_op* ops, long long n, hipStream_t s, float** result) {
-    if (const char* e = launch_scale(p->sb[0], p->noise_stage, d->x0_scale, n, s)) return fail(h, e);
+// The program form is the op list: its terms are kept as given.
+OpList lower_program(const adf_prog_desc* d, const adf_prog_op* ops) {
+    OpList l;
+    l.ops.assign(ops, ops + d->num_ops);
+    l.x0_scale = d->x0_scale; l.result_slot = d->result_slot;
+    return l;
+}
+
+std::vector<float> op_rows(const OpList& l) {
+    std::vector<float> rows;
+    for (const adf_prog_op& o : l.ops)
+        if (o.kind == ADF_PROG_EVAL) rows.insert(rows.end(), {o.eval.c_in, o.eval.c_noise, o.eval.c_skip, o.eval.c_out});
+    return rows;
+}
+
+// Evaluation k of the run (row k of Plan::coef_all, embedded at the head of the run) on x, ending as `e.clip` says.
+static int table_eval(adf_handle* h, Plan* p, int k, const adf_table_eval& e, const float* x, float* out, hipStream_t s) {
+    EvalClip ec;
+    ec.noclip = e.clip == ADF_CLIP_NONE || (e.clip == ADF_CLIP_CONFIGURED && h->unclipped());
+    ec.dyn = e.clip == ADF_CLIP_CONFIGURED && h->dyn_q > 0.0f && !ec.noclip;
+    ec.raw = ec.noclip && e.c_skip == 0.0f && e.c_out == 1.0f;      // the estimate is the network output: written straight into `out`
+    return denoise_io(h, p, row_io(h, p, k, x), out, ec, s);
+}
+
+// The one loop: slot 0 = x0_scale * noise, then the ops in order.  Slots are resolved here, at enqueue time: staging the draws may have moved
+// Plan::inj_stage since the list was lowered.
+int run_ops(adf_handle* h, Plan* p, const OpList& l, long long n, hipStream_t s, float** result) {
+    auto at = [&](int slot) { return slot < kStateSlots ? p->sb[slot] : p->inj_stage + (size_t)(slot - kStateSlots) * n; };
+    if (const char* e = launch_scale(p->sb[0], p->noise_stage, l.x0_scale, n, s)) return fail(h, e);
     int k = 0;
-    for (int i = 0; i < d->num_ops; ++i) {
-        const adf_prog_op& o = ops[i];
+    for (const adf_prog_op& o : l.ops) {
         if (o.kind == ADF_PROG_EVAL) {
-            if (table_eval(h, p, k++, o.eval, p->sb[o.src], p->sb[o.dst], s)) return 1;
+            if (table_eval(h, p, k++, o.eval, at(o.src), at(o.dst), s)) return 1;
             continue;
         }
         LinTerms t;
         memset(&t, 0, sizeof(t));
         t.n = o.n_terms;
-        for (int j = 0; j < o.n_terms; ++j) { t.p[j] = p->sb[o.slot[j]]; t.k[j] = o.coef[j]; }
-        if (const char* e = launch_lin(p->sb[o.dst], t, o.clamp != 0, n, s)) return fail(h, e);
+        for (int j = 0; j < o.n_terms; ++j) { t.p[j] = at(o.slot[j]); t.k[j] = o.coef[j]; }
+        if (const char* e = launch_lin(at(o.dst), t, o.clamp != 0, n, s)) return fail(h, e);
     }
-    *result = p->sb[d->result_slot];
+    *result = at(l.result_slot);
     return 0;
 }
 

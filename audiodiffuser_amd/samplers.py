@@ -28,7 +28,7 @@ from torch import Tensor
 
 from . import _lib
 from .diffusion import Diffusion, EluDiffusion, VDiffusion, conditioning_refusal
-from .net import HipNet, UNet1dBase
+from .net import HipNet
 
 
 # ADF_REQUIRE_NATIVE=1 (or ``samplers.REQUIRE_NATIVE = True``): a sampler call that would NOT run inside libadf_hip.so raises
@@ -65,13 +65,17 @@ def _native_pair(fn: Callable, net, cond_scale: float, kwargs: dict, noise: Opti
     return None
 
 
-def _condition(net: UNet1dBase, hd, x: Tensor, cond_scale: float, kwargs: dict, diff: Diffusion) -> None:
-    """Labels + guidance scale of this sampler run (the reference forwards them to every fn call, e.g.
-    sampler_edm.py:341-345), and the preconditioning and clipping of the owner of ``fn`` (its get_scale_weights; clamp, dynamic
-    threshold or -- VDiffusion -- none, diffusion.py:61, :326)."""
-    diff._configure(hd)
+def _enter(noise: Tensor, net: HipNet, cond_scale: float, kwargs: dict, diff: Optional[Diffusion] = None) -> tuple:
+    """The way into every device loop: (the noise as the library takes it, the handle of ``net``), with the handle set for this run.  ``diff``, where
+    given, sets the preconditioning and clipping of the owner of ``fn`` (its get_scale_weights; clamp, dynamic threshold or -- VDiffusion -- none,
+    diffusion.py:61, :326); then labels + guidance scale (the reference forwards them to every fn call, e.g. sampler_edm.py:341-345)."""
+    x = _prep(noise)
+    hd = net.native(x.device)
+    if diff is not None:
+        diff._configure(hd)
     if net.cfg.class_cond:
         hd.set_condition(kwargs["classes"], x.device, null_labels=False, cond_scale=float(cond_scale))
+    return x, hd
 
 
 def _draws(x: Tensor, n: int, injected: Optional[Tensor], needed: bool) -> Optional[Tensor]:
@@ -116,9 +120,7 @@ class _Sampler(nn.Module):
         diff = _native_pair(fn, net, self.cond_scale, kwargs, noise, type(self).__name__)
         if diff is None:
             return None
-        x = _prep(noise)
-        hd = net.native(x.device)
-        _condition(net, hd, x, self.cond_scale, kwargs, diff)
+        x, hd = _enter(noise, net, self.cond_scale, kwargs, diff)
         plan = self._draw_plan(sigmas)
         inj = _draws(x, plan[0], injected_noise, plan[1]) if plan is not None else None
         return hd.sampler_run(self._desc(diff.sigma_data), sigmas, x, inj).to(noise.dtype)
@@ -151,12 +153,7 @@ class _TableSampler(nn.Module):
                    n_draws: int, injected_noise: Optional[Tensor], configure: bool) -> Tensor:
         """One ``adf_sampler_run_table`` call.  The order is the other samplers': the condition is set before the run, and the draws advance the
         global generator after everything that can refuse."""
-        x = _prep(noise)
-        hd = net.native(x.device)
-        if configure:
-            owner._configure(hd)
-        if net.cfg.class_cond:
-            hd.set_condition(kwargs["classes"], x.device, null_labels=False, cond_scale=float(self.cond_scale))
+        x, hd = _enter(noise, net, self.cond_scale, kwargs, owner if configure else None)
         inj = _draws(x, n_draws, injected_noise, True) if n_draws > 0 else None
         desc = _lib.AdfTableDesc(num_steps=len(steps), x0_scale=x0_scale, final_clamp=int(final_clamp), use_graph=int(self.use_graph))
         return hd.sampler_run_table(desc, (_lib.AdfTableStep * len(steps))(*steps), x, inj).to(noise.dtype)
@@ -1091,10 +1088,7 @@ class _VObjProgramSampler(_VObjTableSampler):
         return None
 
     def _run_program(self, noise: Tensor, net, kwargs: dict, ops: list, x0_scale: float, result_slot: int) -> Tensor:
-        x = _prep(noise)
-        hd = net.native(x.device)
-        if net.cfg.class_cond:
-            hd.set_condition(kwargs["classes"], x.device, null_labels=False, cond_scale=float(self.cond_scale))
+        x, hd = _enter(noise, net, self.cond_scale, kwargs)
         desc = _lib.AdfProgDesc(num_ops=len(ops), result_slot=result_slot, x0_scale=x0_scale, use_graph=int(self.use_graph))
         return hd.sampler_run_program(desc, (_lib.AdfProgOp * len(ops))(*ops), x).to(noise.dtype)
 

@@ -67,7 +67,8 @@ extern "C" {
  *    adf_table_eval and the three ADF_CLIP_* modes (VESampler, VPSampler, VSampler, VEulerSampler).  No ADF_SAMPLER_* or ADF_PRECOND_* kind is added:
  *    adf_sampler_desc, its kinds and adf_set_preconditioning are as they were.
  *    Added without a bump (new symbols only): adf_sampler_run_program and adf_sampler_program_nfe with adf_prog_desc / adf_prog_op and the ADF_PROG_*
- *    constants (VDPMSampler, VUniPCSampler).  adf_table_eval is reused as it is; the table loop and its structs are untouched. */
+ *    constants (VDPMSampler, VUniPCSampler).  adf_table_eval is reused as it is.  The table and the program are two public forms of one
+ *    loop: the library lowers both to one internal op list and one driver runs it; neither form's structs, messages or cache keys depend on that. */
 #define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
@@ -274,7 +275,7 @@ int adf_sampler_run(adf_handle* h, const adf_sampler_desc* desc, const float* si
                     const float* noise, const float* injected_noise, int n_injected, float* out, int B, int L, void* stream);
 int adf_sampler_nfe(const adf_sampler_desc* desc, const float* sigmas_host, int n_sigmas);
 
-/* The table-driven loop: a sampler whose every branch and scalar depends on the schedule and the constructor arguments only, handed over as one
+/* The table form of the op loop: a sampler whose every branch and scalar depends on the schedule and the constructor arguments only, handed over as one
  * host record per step.  What runs VESampler / VPSampler (src/models/components/sampler_edm.py:31-227) and VSampler / VEulerSampler
  * (sampler_vobj.py:31-194); audiodiffuser_amd/samplers.py builds their tables.  With x the fp32 state, eps the record's draw and D a denoiser
  * evaluation out = clip(c_skip x_in + c_out net(c_in x_in, c_noise)), step i is
@@ -326,11 +327,11 @@ int adf_sampler_run_table(adf_handle* h, const adf_table_desc* desc, const adf_t
                           int n_injected, float* out, int B, int L, void* stream);
 int adf_sampler_table_nfe(const adf_table_desc* desc, const adf_table_step* steps);
 
-/* The program-driven loop: a sampler with memory (a linear multistep method) whose every branch and scalar depends on the schedule and the constructor
+/* The program form of the op loop: a sampler with memory (a linear multistep method) whose every branch and scalar depends on the schedule and the constructor
  * arguments only, handed over as a straight-line host program over ADF_PROG_SLOTS state buffers (fp32 [B][C][L] each).  What runs
  * sampler_vobj.DPMSampler and sampler_vobj.UniPCSampler (src/models/components/sampler_vobj.py:196-732); audiodiffuser_amd/samplers.py builds their
  * programs.  Slot 0 starts as x0_scale * noise, every other slot as unwritten.  An op is
- *     ADF_PROG_EVAL   slot[dst] = clip(c_skip x + c_out net(c_in x, c_noise)), x = slot[src]; `eval` is an adf_table_eval, read as in the table loop
+ *     ADF_PROG_EVAL   slot[dst] = clip(c_skip x + c_out net(c_in x, c_noise)), x = slot[src]; `eval` is an adf_table_eval, read as in the table form
  *     ADF_PROG_LIN    slot[dst] = sum_{j < n_terms} coef[j] * slot[slot[j]], 1 <= n_terms <= ADF_PROG_TERMS, clamped to [-1, 1] where clamp != 0;
  *                     one fused pass; dst may be one of the operands
  * and the sample is slot[result_slot] after the last op.  There are no draws.  A method's history (its earlier model outputs) stays where it was

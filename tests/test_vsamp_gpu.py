@@ -306,3 +306,79 @@ def test_malformed_tables_are_refused_by_name_and_launch_nothing():
         assert hd.counters() == before, "a refused call enqueued or counted something"
     y = counted(hd, 1, False, lambda: run_table(hd, [good], noise, None))                     # the handle is as good as before
     assert bool(torch.isfinite(y).all())
+
+
+# ---- the two public forms are one loop: a draw-free table and its program, lowered by hand, give the same bits ------------------------------
+SLOT_X, SLOT_D1, SLOT_XE, SLOT_D2 = 0, 1, 2, 3          # the slots a table's state, first estimate, x_e and second estimate live in
+
+
+def lower_by_hand(steps, final_clamp):
+    """The ``adf_prog_op`` list of a table none of whose records reads a draw, by the rule the library lowers a table with: the a-update unless
+    a0 == 1 and a1 == 0, the evaluation into D1, the b-update (into X, or into XE where a second evaluation and the c-update follow); operands in the
+    order of the step form in the header, those with a zero coefficient dropped; the closing clamp on the last op; the result in slot 0."""
+    def lin(dst, terms, clamp=0):
+        terms = [(s, k) for s, k in terms if k != 0.0]
+        op = _lib.AdfProgOp(kind=_lib.PROG_LIN, dst=dst, n_terms=len(terms), clamp=clamp)
+        for j, (s, k) in enumerate(terms):
+            op.slot[j], op.coef[j] = s, k
+        return op
+
+    def evaluate(dst, src, e):
+        return _lib.AdfProgOp(kind=_lib.PROG_EVAL, dst=dst, src=src, eval=e)
+    ops = []
+    for i, r in enumerate(steps):
+        assert r.a1 == 0.0 and r.b2 == 0.0, "the program form has no draws"
+        clamp = int(bool(final_clamp) and i + 1 == len(steps))
+        if not (r.a0 == 1.0 and r.a1 == 0.0):
+            ops.append(lin(SLOT_X, [(SLOT_X, r.a0)]))
+        ops.append(evaluate(SLOT_D1, SLOT_X, r.eval1))
+        if not r.second:
+            ops.append(lin(SLOT_X, [(SLOT_X, r.b0), (SLOT_D1, r.b1)], clamp))
+            continue
+        ops.append(lin(SLOT_XE, [(SLOT_X, r.b0), (SLOT_D1, r.b1)]))
+        ops.append(evaluate(SLOT_D2, SLOT_XE, r.eval2))
+        ops.append(lin(SLOT_X, [(SLOT_X, r.c0), (SLOT_D1, r.c1), (SLOT_XE, r.c2), (SLOT_D2, r.c3)], clamp))
+    return ops
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["veuler_tiny_heun", "veuler_wn_heun", "v_tiny_cc_guided"])
+def test_a_draw_free_table_and_its_hand_lowered_program_give_the_same_bits(name):
+    """adf_sampler_run_table and adf_sampler_run_program must enqueue the same launches for the same work, so the results are compared with
+    torch.equal, eager and graph-replayed.  veuler_tiny_heun: two-evaluation steps, a one-evaluation last step, ADF_CLIP_NONE rows (the raw-output
+    route).  veuler_wn_heun: 1503 elements, the scalar tail of the update kernel.  v_tiny_cc_guided: NOT a sampler but VSampler's table with every b2
+    set to 0, so no draw is read: ADF_CLIP_UNIT rows on the class-conditional net under cond_scale = 3 (two passes and the guidance combine per
+    evaluation).  Without the noise its state may sit at the clamp; bit equality is the assertion, so nothing is asked of the saturated share, only
+    that the result is finite and not constant."""
+    sp = VC.spec(name)
+    smp = CLS[sp["sampler"]](**VC.sampler_kwargs(sp))
+    steps = smp._table(VC.sigmas_of(sp))[0]
+    if sp["sampler"] == "v":
+        for r in steps:
+            r.b2 = 0.0                       # the hand-made table: VSampler's, without its noise
+    assert all(r.a1 == 0.0 and r.b2 == 0.0 for r in steps)
+    clips = {e.clip for r in steps for e in ([r.eval1, r.eval2] if r.second else [r.eval1])}
+    if sp["sampler"] == "veuler":
+        assert any(r.second for r in steps) and not steps[-1].second and clips == {_lib.CLIP_NONE}
+    else:
+        assert clips == {_lib.CLIP_UNIT} and sp["cond_scale"] == 3.0
+    ops = lower_by_hand(steps, final_clamp=1)
+    assert ops[-1].kind == _lib.PROG_LIN and ops[-1].clamp == 1 and sum(o.clamp for o in ops) == 1
+    nfe = table_nfe(steps)
+    pd = _lib.AdfProgDesc(num_ops=len(ops), result_slot=SLOT_X, x0_scale=1.0, use_graph=0)
+    assert nfe == sum(o.kind == _lib.PROG_EVAL for o in ops) == _lib.load_library().adf_sampler_program_nfe(C.byref(pd), (_lib.AdfProgOp * len(ops))(*ops))
+    net = device_net(sp["net"], sp["out_scale"])
+    hd, noise = handle(net), VC.noise_of(sp).cuda()
+    if sp["net"] == "wn":
+        assert noise.numel() % 4 == 3
+    cl = RC.labels(sp["net"])
+    if cl is not None:
+        hd.set_condition(cl.cuda(), noise.device, null_labels=False, cond_scale=sp["cond_scale"])
+    for use_graph in (0, 1):
+        pd = _lib.AdfProgDesc(num_ops=len(ops), result_slot=SLOT_X, x0_scale=1.0, use_graph=use_graph)
+        yt = counted(hd, nfe, use_graph, lambda: run_table(hd, steps, noise, None, x0=1.0, clamp=1, use_graph=use_graph).cpu())
+        yp = counted(hd, nfe, use_graph, lambda: hd.sampler_run_program(pd, (_lib.AdfProgOp * len(ops))(*ops), noise).cpu())
+        print(name, "graph" if use_graph else "eager", "differing entries", int((yt != yp).sum()), "of", yt.numel(), "max |y|", float(yt.abs().max()),
+              "share |y| >= 1", float((yt.abs() >= 1).float().mean()))
+        assert bool(torch.isfinite(yt).all()) and float(yt.min()) < float(yt.max())
+        assert torch.equal(yt, yp), (name, use_graph)
