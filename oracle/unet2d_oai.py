@@ -9,6 +9,9 @@ the build container by ``oracle/gen_golden_next.py``; fixtures in ``tests/golden
 Every function cites the reference lines it restates (paths relative to the reference repo root; all line
 numbers are in ``src/models/backbones/unet2d_oai.py`` unless another file is named).
 
+Float64 weights, inputs and times give a float64 run (every tap and the output float64): the places where the reference says ``.float()`` follow the
+dtype of their input; on fp32 inputs nothing changes (oracle/adm_sweep.py, tests/test_oracle_adm_sweep.py).  The bf16-storage branch keeps its explicit fp32.
+
 Arithmetic modes as in oracle/unet1d.py.  ``storage="bf16"`` rounds where the HIP throughput mode of adf_conv2d.hip holds bf16:
 every stored activation, the activated conv operand ``silu(a x + b)``, the GEMM weights; a conv with a residual stores
 ``r(r(conv + bias) + residual)`` (its output tile is rounded in LDS before the residual is added); GroupNorm statistics are those
@@ -37,15 +40,16 @@ from audiodiffuser_amd.adm_config import (ADMConfig, config_c4, config_c4_small,
 
 # ------------------------------------------------------------------ pieces
 def group_norm32(p: P, pre: str, x: torch.Tensor) -> torch.Tensor:
-    """:10-21 -- GroupNorm(32, C), eps 1e-5, computed in fp32."""
-    return F.group_norm(x.float(), 32, p[f"{pre}.weight"], p[f"{pre}.bias"], 1e-5)
+    """:10-21 -- GroupNorm(32, C), eps 1e-5, computed in fp32 (the reference's ``x.float()``); a float64 input (the float64 oracle run) stays float64."""
+    return F.group_norm(x if x.dtype == torch.float64 else x.float(), 32, p[f"{pre}.weight"], p[f"{pre}.bias"], 1e-5)
 
 
 def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0) -> torch.Tensor:
-    """:31-49 -- fixed sinusoidal features, cosines first."""
+    """:31-49 -- fixed sinusoidal features, cosines first.  fp32 as in the reference; float64 times give float64 features."""
     half = dim // 2
-    freqs = torch.exp(-math.log(max_period) * torch.arange(half, dtype=torch.float32) / half)
-    args = t[:, None].float() * freqs[None]
+    dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+    freqs = torch.exp(-math.log(max_period) * torch.arange(half, dtype=dt) / half)
+    args = t[:, None].to(dt) * freqs[None]
     emb = torch.cat([torch.cos(args), torch.sin(args)], dim=-1)
     if dim % 2:
         emb = torch.cat([emb, torch.zeros_like(emb[:, :1])], dim=-1)
@@ -118,7 +122,7 @@ def qkv_attention(qkv: torch.Tensor, heads: int, legacy: bool, st: Optional["Sto
     """:324-350 (legacy: heads split first, each head's rows are q|k|v) and :352-380 (new order: q|k|v split first).
     Both scale q and k by ch^-1/4 and take the softmax in fp32.  bf16 storage (``st``) on the shapes the device serves with its MFMA attention
     kernel: the un-normalised probabilities are rounded as the matrix operand of P V while the normaliser sums the unrounded ones (as
-    oracle/unet1d.py self_attention)."""
+    oracle/unet1d.py self_attention), per tile of 32 keys and relative to the running maximum, as the kernel's online softmax has them."""
     b, width, n = qkv.shape
     ch = width // (3 * heads)
     if legacy:
@@ -128,9 +132,19 @@ def qkv_attention(qkv: torch.Tensor, heads: int, legacy: bool, st: Optional["Sto
     scale = 1 / math.sqrt(math.sqrt(ch))
     w = torch.einsum("bct,bcs->bts", q * scale, k * scale)
     if st is not None and st.bf16 and mfma_attention(ch, n):
-        pr = torch.exp(w.float() - w.float().amax(dim=-1, keepdim=True))
-        return (torch.einsum("bts,bcs->bct", st.r(pr), v) / pr.sum(dim=-1).unsqueeze(1)).reshape(b, -1, n)
-    w = torch.softmax(w.float(), dim=-1)
+        # attention_mfma32_kernel walks the keys in tiles of 32 with a running maximum per query: the probabilities of a tile are rounded RELATIVE TO THE
+        # MAXIMUM SO FAR, exp(w - m_tile), and the tile's share of P V is rescaled to the final maximum in fp32 afterwards.  Rounding exp(w - global max)
+        # instead flips about every rounding of P after a query's maximum has grown: 9.5e-4 of an ``.att`` at 64 and 128 tokens, where few keys average it
+        # out (tests/test_adm_sweep_gpu.py flat_w64 / lv3_w64), against 5e-5 at 1024
+        nt = -(-n // 32)
+        wt = (F.pad(w.float(), (0, nt * 32 - n), value=float("-inf")) if n % 32 else w.float()).reshape(*w.shape[:2], nt, 32)
+        m = wt.amax(dim=-1, keepdim=True).cummax(dim=-2).values                                # [b, query, tile, 1]: the maximum after each tile
+        pr = torch.exp(wt - m)
+        back = torch.exp(m - m[:, :, -1:])                                                     # the later rescales of the tile's accumulator share
+        den = (pr.sum(dim=-1, keepdim=True) * back).sum(dim=-2)                                # [b, query, 1]
+        pv = (st.r(pr) * back).reshape(*w.shape[:2], nt * 32)[..., :n]
+        return (torch.einsum("bts,bcs->bct", pv, v) / den.transpose(1, 2)).reshape(b, -1, n)
+    w = torch.softmax(w if w.dtype == torch.float64 else w.float(), dim=-1)      # float64 scores (the float64 oracle run) stay float64
     return torch.einsum("bts,bcs->bct", w, v).reshape(b, -1, n)
 
 
