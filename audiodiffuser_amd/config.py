@@ -79,6 +79,19 @@ class UNet1dConfig:
         ch, n, g = self.channels, self.num_layers, self.resnet_groups
         if self.window_length > 16:
             raise ValueError(f"unet.to_out: window_length up to 16 is served, got {self.window_length}")
+        # the reference pads both transforms by window_length // 2 - stride // 2 (unet1d.py:584-591, :611-622).  torch refuses a negative padding, and with a
+        # window and a stride of different parity 2 * pad != window_length - stride: its ConvTranspose1d returns L - 1 or L + 1 samples (and its to_in may
+        # return one row less than L / stride) where the device writes L.  adf_create (csrc/adf_net_unet1d.hip) refuses the same three.
+        if self.stride < 1:
+            raise ValueError(f"unet.to_in / unet.to_out: stride must be at least 1, got {self.stride}")
+        if self.stride > self.window_length:
+            raise ValueError(f"unet.to_in / unet.to_out: stride = {self.stride} above window_length = {self.window_length} makes the reference's padding "
+                             "negative, which torch refuses")
+        if (self.window_length - self.stride) % 2:
+            raise ValueError(f"unet.to_in / unet.to_out: window_length = {self.window_length} and stride = {self.stride} of different parity: the reference's "
+                             "padding (window_length // 2 - stride // 2) no longer gives L samples back")
+        if self.class_cond and ch > 512:
+            raise ValueError(f"label_conditioner: a class-conditional net of up to 512 channels is served (launch_class_embed), got {ch}")
         if not self.use_nearest_upsample:
             for u, i in enumerate(reversed(range(n))):
                 if self.factors[i] < 2:

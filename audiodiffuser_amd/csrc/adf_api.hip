@@ -116,6 +116,7 @@ static int stage_injected(adf_handle* h, Plan* p, const float* injected_noise, s
 static int reserve_eval_tables(adf_handle* h, Plan* p, int n_eval) {
     const NetDims& nd = h->net->dims;
     p->pre_rows = n_eval;
+    p->den_rows = 0;
     if (n_eval <= p->pre_cap) return 0;
     if (p->pre_cap) {
         (void)hipDeviceSynchronize();
@@ -349,6 +350,7 @@ int adf_net_forward(adf_handle* h, const float* x, const float* t, float* out, i
     if (get_plan(h, B, L, s, &p)) return 1;
     FwdIO io;
     io.x = x; io.out = out; io.t = t; io.t_stride = 1; io.nb = B;
+    p->cfg_live = false;
     if (cond_rows(h, B, false, io)) return 1;
     return forward(h, p, io, s);
 }
@@ -426,6 +428,7 @@ int adf_denoise(adf_handle* h, const float* x_noisy, const float* sigmas_dev, fl
     Plan* p;
     if (get_plan(h, B, L, s, &p)) return 1;
     ++h->ctr.denoise_calls;
+    p->den_rows = sigmas_dev ? B : 1;                      // (adf_debug_coef_rows: the rows this call leaves in Plan::coef)
     if (!sigmas_dev) return denoise_scalar(h, p, x_noisy, sigma, sigma_data, out, s);
     return denoise_rows(h, p, x_noisy, sigmas_dev, sigma_data, out, s);
 }
@@ -598,11 +601,13 @@ int adf_debug_dyn_threshold(adf_handle* h, float* x_dev, int B, long long per_sa
 
 int adf_debug_coef_rows(adf_handle* h, float* out_dev, int max_rows, int* n_rows, void* stream) {
     ADF_ON_DEVICE(h);
-    if (!h->last_plan || !h->last_plan->coef_all) return fail(h, "adf_debug_coef_rows: no sampler run yet");
+    if (!h->last_plan || (!h->last_plan->coef_all && !h->last_plan->den_rows)) return fail(h, "adf_debug_coef_rows: no sampler run or adf_denoise call yet");
     const Plan* p = h->last_plan;
-    if (n_rows) *n_rows = p->pre_rows;
-    const int n = std::min(max_rows, p->pre_rows);
-    if (n > 0 && out_dev && hipMemcpyAsync(out_dev, p->coef_all, (size_t)n * 4 * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+    const int rows = p->den_rows ? p->den_rows : p->pre_rows;
+    const float* src = p->den_rows ? p->coef : p->coef_all;
+    if (n_rows) *n_rows = rows;
+    const int n = std::min(max_rows, rows);
+    if (n > 0 && out_dev && hipMemcpyAsync(out_dev, src, (size_t)n * 4 * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
         return fail(h, "adf_debug_coef_rows: copy failed");
     return 0;
 }
@@ -614,6 +619,13 @@ const char* adf_debug_tap_name(adf_handle* h, int i) {
 }
 int adf_debug_tap_shape(adf_handle* h, const char* name, int* C, int* L) {
     if (!h->last_plan) return fail(h, "no forward has run yet");
+    // the label embedding of the last adf_set_condition: handle state, [cond_B][cdim] fp32 (the null row behind it is not part of the tap)
+    if (h->cdim > 0 && h->cond_on && std::string(name) == "class_emb") { *C = h->cdim; *L = 1; return 0; }
+    // the raw passes (labels, null labels) of the last evaluation, where it ran under guidance: fp32 [B][out_channels][L] as the combine kernel read them
+    if (h->last_plan->cfg_live && (std::string(name) == "cfg.cond" || std::string(name) == "cfg.null")) {
+        *C = h->net->dims.out_channels; *L = h->last_plan->L;
+        return 0;
+    }
     for (const auto& t : h->last_plan->taps)
         if (t.name == name) { *C = t.C; *L = t.L; return 0; }
     return fail(h, std::string("unknown tap ") + name);
@@ -621,6 +633,19 @@ int adf_debug_tap_shape(adf_handle* h, const char* name, int* C, int* L) {
 int adf_debug_tap_copy(adf_handle* h, const char* name, float* out, void* stream) {
     ADF_ON_DEVICE(h);
     if (!h->last_plan) return fail(h, "no forward has run yet");
+    if (h->cdim > 0 && h->cond_on && std::string(name) == "class_emb") {
+        if (h->cond_B != h->last_plan->B) return fail(h, "adf_debug_tap_copy: class_emb belongs to another batch size than the last forward");
+        if (hipMemcpyAsync(out, h->cond_emb, (size_t)h->cond_B * h->cdim * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+            return fail(h, "adf_debug_tap_copy: copy failed");
+        return 0;
+    }
+    if (h->last_plan->cfg_live && (std::string(name) == "cfg.cond" || std::string(name) == "cfg.null")) {
+        const Plan* p = h->last_plan;
+        const size_t bytes = (size_t)p->B * h->net->dims.out_channels * p->L * 4;
+        if (hipMemcpyAsync(out, std::string(name) == "cfg.cond" ? p->cfg_c : p->cfg_n, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
+            return fail(h, "adf_debug_tap_copy: copy failed");
+        return 0;
+    }
     for (const auto& t : h->last_plan->taps)
         if (t.name == name) {
             const char* e = launch_nlc_to_ncl_f32(t.p, out, t.f32 ? 0 : h->bf16, h->last_plan->B, t.L, t.C, (hipStream_t)stream);

@@ -76,10 +76,12 @@ struct Plan {
     float *coef_all = nullptr, *temb_all = nullptr, *film_all = nullptr;
     int pre_cap = 0;
     int pre_rows = 0;                                     // rows of coef_all the last sampler run filled (adf_debug_coef_rows)
+    int den_rows = 0;                                     // rows of coef the last adf_denoise call filled, if that was the plan's last evaluation (else 0)
     // sampler state (fp32 [B][C][L] each)
     float* sb[10] = {nullptr};
     float* noise_stage = nullptr; float* out_stage = nullptr; float* inj_stage = nullptr; size_t inj_cap = 0;
     float* cfg_c = nullptr; float* cfg_n = nullptr;      // raw network outputs of the two CFG branches
+    bool cfg_live = false;                               // both hold the two passes of the plan's last evaluation (adf_debug_tap_copy "cfg.cond" / "cfg.null")
     float* dyn_scale = nullptr;                          // [B] per-sample scales of the dynamic threshold
     double* loss_partial = nullptr;                      // [B][loss_chunks(C * L)] block sums of adf_diffusion_loss, allocated by the first loss call on this plan
     // captured sampler loops, most recently used first; at most kMaxGraphsPerPlan are kept (the oldest is destroyed)

@@ -533,6 +533,11 @@ extern "C" int adf_create(const adf_net_config* cfg, adf_handle** out) {
     if (c.num_filters != c.channels * c.multipliers[0]) { g_create_error = "adf_create: num_filters must equal channels*multipliers[0]"; return 1; }
     if (c.channels % 2 || c.channels < 2) { g_create_error = "adf_create: channels must be even"; return 1; }
     if (c.dtype != ADF_DTYPE_F32 && c.dtype != ADF_DTYPE_BF16 && c.dtype != ADF_DTYPE_F32X3) { g_create_error = "adf_create: bad dtype"; return 1; }
+    // (UNet1dConfig.validate_device restates the three checks below.)  The reference pads by window / 2 - stride / 2 (unet1d.py:584-591, :611-622): with a window
+    // and a stride of different parity 2 pad != window - stride and its transposed conv returns L - 1 or L + 1 samples, where to_out writes L
+    if (c.stride < 1) { g_create_error = "adf_create: unet.to_in / unet.to_out: stride must be at least 1"; return 1; }
+    if (c.stride > c.window_length) { g_create_error = "adf_create: unet.to_in / unet.to_out: stride above window_length (negative padding)"; return 1; }
+    if ((c.window_length - c.stride) % 2) { g_create_error = "adf_create: unet.to_in / unet.to_out: window_length and stride of different parity"; return 1; }
     auto net = std::make_unique<Unet1dNet>();
     net->cfg = c;
     NetDims& d = net->dims;

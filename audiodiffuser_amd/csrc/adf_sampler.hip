@@ -49,6 +49,7 @@ int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, hipStream_t s) { re
 int denoise_io(adf_handle* h, Plan* p, FwdIO io, float* out, const EvalClip& ec, hipStream_t s) {
     const bool cfg = h->cdim > 0 && h->cond_on && h->cond_scale != 1.0f;
     const bool noclip = ec.noclip, raw = ec.raw, dyn = ec.dyn;
+    p->cfg_live = cfg;
     // one pass with the preconditioning in the last kernel's epilogue: clamped on every net, unclipped on UNet2dBase (u2d_conv_out_raw_kernel mode 2);
     // the raw kind is the mode 0 pass written straight into `out` on every net
     if (!cfg && !dyn && (!noclip || raw || h->net->unclipped_epilogue)) {

@@ -369,7 +369,9 @@ int adf_sampler_run_program(adf_handle* h, const adf_prog_desc* desc, const adf_
 int adf_sampler_program_nfe(const adf_prog_desc* desc, const adf_prog_op* ops);
 
 /* Parity-test support: copy an internal activation of the LAST adf_net_forward/adf_denoise call, converted to
- * fp32 [B][C][L].  Names follow oracle/unet1d.py taps ("to_in", "down0.conv", "down0.block1", "mid.attn", ...). */
+ * fp32 [B][C][L].  Names follow oracle/unet1d.py taps ("to_in", "down0.conv", "down0.block1", "mid.attn", ...).  "class_emb" (not among
+ * adf_debug_tap_name's): the [B][cdim][1] label embedding of the last adf_set_condition, while a condition is set.  "cfg.cond" / "cfg.null"
+ * (likewise): the two raw network outputs [B][out_channels][L] of the last evaluation, where it ran under guidance (cond_scale != 1). */
 int adf_debug_tap_shape(adf_handle* h, const char* name, int* C, int* L);
 int adf_debug_tap_copy(adf_handle* h, const char* name, float* out_fp32, void* stream);
 /* The GroupNorm statistics that the launch which stored tap `name` reduced with it: [B][groups][2] doubles (sum, sum of squares per sample and
@@ -389,7 +391,8 @@ int adf_debug_rb_block_plan(int K, int f, int C, int phase_c, int n, int B, int 
 /* The dynamic threshold alone, in place on x_dev [B][per_sample] (tests: exactness of the order statistics against torch.quantile). */
 int adf_debug_dyn_threshold(adf_handle* h, float* x_dev, int B, long long per_sample, float quantile, void* stream);
 /* The (c_in, c_noise, c_skip, c_out) rows of the last adf_sampler_run on this handle, one per denoiser evaluation in order: copies
- * min(max_rows, rows) * 4 floats to out_dev (device) and returns the number of rows of that run through *n_rows. */
+ * min(max_rows, rows) * 4 floats to out_dev (device) and returns the number of rows of that run through *n_rows.  After an adf_denoise call
+ * at the same shape: the rows of that call instead (one for a scalar sigma, B for per-sample sigmas). */
 int adf_debug_coef_rows(adf_handle* h, float* out_dev, int max_rows, int* n_rows, void* stream);
 int adf_debug_tap_count(adf_handle* h);
 const char* adf_debug_tap_name(adf_handle* h, int index);

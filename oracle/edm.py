@@ -49,6 +49,8 @@ def denoise(net: Callable[..., torch.Tensor], x_noisy: torch.Tensor,
     b = x_noisy.shape[0]
     if sigmas is None:
         sigmas = torch.full((b,), float(sigma), dtype=torch.float32)   # components/utils.py:41-52
+    if x_noisy.dtype == torch.float64:          # the float64 run (a reference for the device's fp32): the fp32 sigma values, every coefficient in float64
+        sigmas = sigmas.to(torch.float64)
     c_skip, c_out, c_in, c_noise = edm_scale_weights(sigmas, sigma_data, x_noisy.ndim)
     if cond_scale == 1.0:
         pred = net(c_in * x_noisy, c_noise)

@@ -22,7 +22,7 @@ PRIMES = (7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 53, 59, 61, 67, 71, 73,
 PER_CASE = 12000            # values of strided block outputs per case
 
 
-def hooked_forward(net, x, t):
+def hooked_forward(net, x, t, classes=None, cond_drop_prob=0.0):
     taps, hs = {}, []
     u = net.unet
 
@@ -45,7 +45,9 @@ def hooked_forward(net, x, t):
         if up.use_attention:
             add(up.transformer, f"up{k}.attn")
         add(up.upsample, f"up{k}.conv")
-    y = net(x, t, cond_drop_prob=0.0)
+    if classes is not None:
+        add(net.label_conditioner, "class_emb")
+    y = net(x, t, classes=classes, cond_drop_prob=cond_drop_prob)
     for h in hs:
         h.remove()
     return y, taps

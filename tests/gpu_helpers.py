@@ -160,12 +160,14 @@ def sweep_make(cfg, w, dtype, flags=0):
 SWEEP_TROUBLE = []        # a device run that raised (a refusal of the library, or a fault that surfaces as an ordinary error): the caller starts nothing after it
 
 
-def sweep_device_run(net, x, t, only=None):
-    """-> (output, {name: recorded tensor}, names in walk order), all on the host.  ``only``: the recorded names to copy back (default: all of them)."""
+def sweep_device_run(net, x, t, only=None, classes=None, cond_drop_prob=None):
+    """-> (output, {name: recorded tensor}, names in walk order), all on the host.  ``only``: the recorded names to copy back (default: all of them).
+    ``classes`` / ``cond_drop_prob``: the labels of a class-conditional net and whether they are dropped (1) or kept (0 or None)."""
     dev = torch.device("cuda", torch.cuda.current_device())
+    kw = {} if classes is None else {"classes": classes.cuda(), "cond_drop_prob": cond_drop_prob}
     try:
         with torch.no_grad():
-            y = net(x.cuda(), t.cuda())
+            y = net(x.cuda(), t.cuda(), **kw)
         torch.cuda.synchronize()
     except Exception as e:
         # a refusal of the library ("<launcher>: <reason>") leaves the device as it was; anything else, or a HIP call that failed, may not
@@ -176,15 +178,19 @@ def sweep_device_run(net, x, t, only=None):
     names = hd.tap_names()
     assert len(names) == len(set(names))
     got = {k: hd.tap(k, x.shape[0], dev).cpu() for k in names if only is None or k in only}
+    if classes is not None:     # the label embedding is handle state, not a tensor of the walk: read under the oracle's name, [B, 4 * channels], first in order
+        names = ["class_emb"] + names
+        if only is None or "class_emb" in only:
+            got["class_emb"] = hd.tap("class_emb", x.shape[0], dev).cpu().squeeze(-1)
     return y.cpu(), got, names
 
 
-def sweep_fp32_report(cfg, w, w64, x, t, net, oracle=None):
-    """fp32 / f32x3 device run against the float64 oracle.  ``oracle``: a (y64, taps64, dist) triple already computed for these inputs."""
+def sweep_fp32_report(cfg, w, w64, x, t, net, oracle=None, classes=None, cond_drop_prob=None):
+    """fp32 / f32x3 device run against the float64 oracle.  ``oracle``: a (y64, taps64, dist) triple already computed for these inputs (and labels)."""
     t0 = time.time()
-    y, got, names = sweep_device_run(net, x, t)
+    y, got, names = sweep_device_run(net, x, t, classes=classes, cond_drop_prob=cond_drop_prob)
     t1 = time.time()
-    y64, t64, dist = oracle if oracle is not None else SW.float64_run(cfg, w, w64, x, t)
+    y64, t64, dist = oracle if oracle is not None else SW.float64_run(cfg, w, w64, x, t, classes=classes, cond_drop_prob=cond_drop_prob or 0.0)
     missing = [k for k in names if k not in t64]
     errs = {}
     for k in names:
@@ -197,14 +203,14 @@ def sweep_fp32_report(cfg, w, w64, x, t, net, oracle=None):
             "device_seconds": t1 - t0, "oracle_seconds": time.time() - t1, "y": y, "got": got}
 
 
-def sweep_x3_report(cfg, w, w64, x, t, net, oracle=None):
+def sweep_x3_report(cfg, w, w64, x, t, net, oracle=None, classes=None, cond_drop_prob=None):
     """f32x3 device run, ONE run held two ways.  ``taps`` / ``out``: every recorded tensor teacher-forced against the split-bf16 oracle (oracle/unet1d.py
     storage="f32x3": relative L2 of one launch on the device's own inputs; the output from the device's last tensor), bar SW.X3_LAUNCH_TOL.  ``free`` /
     ``free_out``: the same tensors free-running against the float64 oracle (max-norm relative), bar F32X3_TOL.  ``oracle``: as in sweep_fp32_report."""
     t0 = time.time()
-    y, got, names = sweep_device_run(net, x, t)
+    y, got, names = sweep_device_run(net, x, t, classes=classes, cond_drop_prob=cond_drop_prob)
     t1 = time.time()
-    y64, t64, dist = oracle if oracle is not None else SW.float64_run(cfg, w, w64, x, t)
+    y64, t64, dist = oracle if oracle is not None else SW.float64_run(cfg, w, w64, x, t, classes=classes, cond_drop_prob=cond_drop_prob or 0.0)
     finite = bool(torch.isfinite(y).all()) and all(bool(torch.isfinite(v).all()) for v in got.values())
     missing = [k for k in names if k not in t64]
     free = {}
@@ -215,7 +221,8 @@ def sweep_x3_report(cfg, w, w64, x, t, net, oracle=None):
     assert y.shape == y64.shape
     forced = {}
     with torch.no_grad():
-        y_f = O.unet1d_forward(w64, cfg, x.double(), t.double(), storage="f32x3", force=got, errs=forced)
+        y_f = O.unet1d_forward(w64, cfg, x.double(), t.double(), storage="f32x3", force=got, errs=forced, classes=classes,
+                               cond_drop_prob=cond_drop_prob or 0.0)
     missing += sorted(set(got) - set(forced))
     if not finite:
         forced = {k: float("inf") for k in forced}
@@ -226,14 +233,14 @@ def sweep_x3_report(cfg, w, w64, x, t, net, oracle=None):
             "device_seconds": t1 - t0, "oracle_seconds": time.time() - t1, "y": y, "got": got}
 
 
-def sweep_bf16_report(cfg, w, x, t, net):
+def sweep_bf16_report(cfg, w, x, t, net, classes=None, cond_drop_prob=None):
     """bf16 device run, every stored tensor teacher-forced against the bf16-storage oracle."""
     t0 = time.time()
-    y, got, names = sweep_device_run(net, x, t)
+    y, got, names = sweep_device_run(net, x, t, classes=classes, cond_drop_prob=cond_drop_prob)
     t1 = time.time()
     forced = {}
     with torch.no_grad():
-        y_f = O.unet1d_forward(w, cfg, x, t, storage="bf16", force=got, errs=forced)
+        y_f = O.unet1d_forward(w, cfg, x, t, storage="bf16", force=got, errs=forced, classes=classes, cond_drop_prob=cond_drop_prob or 0.0)
     missing = sorted(set(got) - set(forced))
     finite = bool(torch.isfinite(y).all()) and all(bool(torch.isfinite(v).all()) for v in got.values())
     return {"taps": forced, "names": names, "missing": missing, "out": O.rel_l2(y, y_f) if finite else float("inf"),
