@@ -1,7 +1,7 @@
 """MI355X-native EDM sampling hot path of AudioDiffuser.
 
 Plugin surface (hydra ``_target_`` s): ``audiodiffuser_amd.UNet1dBase`` / ``audiodiffuser_amd.WaveNetNoise`` / ``audiodiffuser_amd.UNetModel`` /
-``audiodiffuser_amd.UNet2dBase`` (model.net),
+``audiodiffuser_amd.UNet2dBase`` / ``audiodiffuser_amd.DiT`` (the adaLN-Zero transformer, exact fp32) (model.net),
 ``audiodiffuser_amd.EluDiffusion`` / ``VEDiffusion`` / ``VPDiffusion`` / ``VDiffusion`` / ``ReFlow`` (model.diffusion), ``audiodiffuser_amd.EDMSampler`` /
 ``EDMAlphaSampler`` / ``DPMSampler`` / ``DPM2Sampler`` / ``DPM2MSampler`` / ``ADPM2Sampler`` / ``ADPMPP2SSampler`` / ``LMSSampler`` / ``UniPCSampler`` /
 ``ReflowEulerSampler`` / ``VESampler`` / ``VPSampler`` / ``VSampler`` / ``VEulerSampler`` / ``VDPMSampler`` / ``VUniPCSampler`` (model.sampler), ``audiodiffuser_amd.KarrasSchedule`` / ``VESchedule`` / ``VPSchedule`` / ``VSchedule`` / ``LinearSchedule`` /
@@ -19,6 +19,7 @@ from .adm import UNetModel  # noqa: F401
 from .adm_config import ADMConfig, config_c4, config_c4_small  # noqa: F401
 from .unet2d import UNet2dBase  # noqa: F401
 from .unet2d_config import UNet2dConfig  # noqa: F401
+from .dit import DiT, DiTConfig  # noqa: F401
 from .diffusion import EluDiffusion, VEDiffusion, VPDiffusion, VDiffusion, ReFlow  # noqa: F401
 from .samplers import EDMSampler, EDMAlphaSampler, DPMSampler, DPM2Sampler, DPM2MSampler, ADPM2Sampler, ADPMPP2SSampler, LMSSampler, UniPCSampler  # noqa: F401
 from .samplers import ReflowEulerSampler, VESampler, VPSampler, VSampler, VEulerSampler, VDPMSampler, VUniPCSampler  # noqa: F401

@@ -128,6 +128,13 @@ class AdfUNet2dConfig(C.Structure):
                 ("scale_skip_connection", C.c_int32), ("final_resnet_block", C.c_int32), ("dtype", C.c_int32)]
 
 
+class AdfDitConfig(C.Structure):
+    """``adf_dit_config`` of include/audiodiffuser_amd.h."""
+    _fields_ = [("input_h", C.c_int32), ("input_w", C.c_int32), ("patch_h", C.c_int32), ("patch_w", C.c_int32), ("in_channels", C.c_int32),
+                ("hidden_size", C.c_int32), ("depth", C.c_int32), ("num_heads", C.c_int32), ("mlp_hidden", C.c_int32), ("num_classes", C.c_int32),
+                ("dtype", C.c_int32)]
+
+
 class AdfRunCounters(C.Structure):
     """``adf_run_counters`` of include/audiodiffuser_amd.h."""
     _fields_ = [("sampler_runs", C.c_int64), ("sampler_evals", C.c_int64), ("graph_captures", C.c_int64),
@@ -155,6 +162,7 @@ EXPORTS = {
     "adf_wavenet_create": (C.c_int, [C.POINTER(AdfWaveNetConfig), C.POINTER(C.c_void_p)]),
     "adf_adm_create": (C.c_int, [C.POINTER(AdfAdmConfig), C.POINTER(C.c_void_p)]),
     "adf_unet2d_create": (C.c_int, [C.POINTER(AdfUNet2dConfig), C.POINTER(C.c_void_p)]),
+    "adf_dit_create": (C.c_int, [C.POINTER(AdfDitConfig), C.POINTER(C.c_void_p)]),
     "adf_set_image_shape": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "adf_set_dynamic_threshold": (C.c_int, [C.c_void_p, C.c_float]),
     "adf_set_preconditioning": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]),
@@ -298,6 +306,18 @@ def make_unet2d_config(cfg, dtype: int) -> AdfUNet2dConfig:
         c.init_kernel_sizes[i] = int(k)
     c.learned_sinu_pos_emb_dim, c.num_time_tokens = cfg.learned_sinu_pos_emb_dim, cfg.num_time_tokens
     c.scale_skip_connection, c.final_resnet_block = int(cfg.scale_skip_connection), int(cfg.final_resnet_block)
+    c.dtype = dtype
+    return c
+
+
+def make_dit_config(cfg, dtype: int) -> AdfDitConfig:
+    """From an ``audiodiffuser_amd.dit.DiTConfig``."""
+    c = AdfDitConfig()
+    c.input_h, c.input_w = int(cfg.input_size[0]), int(cfg.input_size[1])
+    c.patch_h, c.patch_w = int(cfg.patch_size[0]), int(cfg.patch_size[1])
+    c.in_channels, c.hidden_size, c.depth, c.num_heads = cfg.in_channels, cfg.hidden_size, cfg.depth, cfg.num_heads
+    c.mlp_hidden = cfg.mlp_hidden
+    c.num_classes = int(cfg.num_classes) if cfg.class_cond else 0
     c.dtype = dtype
     return c
 

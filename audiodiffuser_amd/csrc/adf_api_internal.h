@@ -5,6 +5,7 @@
 //   adf_net_wavenet.hip    WavenetNet (declared in adf_net_wavenet.h): WaveNetNoise (wavenet.py:153-180): adf_wavenet_create, registry, walk
 //   adf_net_adm.hip        AdmNet: ADM UNetModel (unet2d_oai.py:382-635): adf_adm_create, registry, walk
 //   adf_net_unet2d.hip     Unet2dNet: Imagen-style UNet2dBase (unet2d.py:622-972), exact fp32: adf_unet2d_create, registry, walk
+//   adf_net_dit.hip        DitNet: the adaLN-Zero transformer DiT (dit.py:278-429), exact fp32: adf_dit_create, registry, walk (kernels: adf_dit.h)
 //   adf_walk2d.h           what the two 2-D walks share: fine GroupNorm statistics, the conv launch, the conditioning prologue
 //   adf_sampler.hip        denoise wrappers; the eleven sampler drivers (sampler_edm.py, stochastic_sampler_edm.py, sampler_rf.py), written on SamplerCtx's
 //                          members (below), which own the split between the counting pass and the real pass; count_sampler, sampler_draws; the op
@@ -101,7 +102,7 @@ struct FwdIO {
     const float* x = nullptr; float* out = nullptr;
     const float* t = nullptr; int t_stride = 0; int nb = 0;
     const float* coef = nullptr; int coef_bstride = 0; const float* x_noisy = nullptr;
-    int mode = 0;                                          // 0: raw network output; 1: clamp(c_skip x_noisy + c_out F, -1, 1); 2: the same unclipped (UNet2dBase only)
+    int mode = 0;                                          // 0: raw network output; 1: clamp(c_skip x_noisy + c_out F, -1, 1); 2: the same unclipped (UNet2dBase, DiT)
     const float* film2 = nullptr; int film2_bstride = 0;   // class part of the FiLM projections (rows of adf_handle::cond_film)
     const float* film_pre = nullptr;                       // this evaluation's row of Plan::film_all: sigma embedding + FiLM already computed
     const float* temb_pre = nullptr;                       // this evaluation's row of Plan::temb_all (class-conditional ADM net: the FiLM rows are per sample)
@@ -123,7 +124,7 @@ struct Net {
     // the class embedding is added to the time embedding before the FiLM projections, so the FiLM rows are per sample (UNetModel, unet2d_oai.py:621-623;
     // UNet2dBase, unet2d.py:902-908); false: the class columns are projected on their own into adf_handle::cond_film (UNet1dBase, unet1d.py:272)
     bool class_in_temb = false;
-    bool unclipped_epilogue = false;    // the last kernel has the FwdIO mode 2 epilogue (only UNet2dBase)
+    bool unclipped_epilogue = false;    // the last kernel has the FwdIO mode 2 epilogue (UNet2dBase, DiT)
     // inputs are images [B][C][H][W]: adf_set_image_shape gives the shape behind the length argument L = H * W of the calls that follow
     bool image = false;
     int H = 0, W = 0;
@@ -276,16 +277,17 @@ struct Registrar {
         if (bias) w.bias = reg_f32(pre + ".bias", cout);
     }
     // LabelEmbedder(num_classes, width_in, width_out) (conditioner.py:64-90): sets the handle's lab_* tensors and cdim
-    void label_embedder(int width_in, int width_out, int num_classes) {
+    // (`module`: the attribute the network keeps it under -- DiT's is y_embedder)
+    void label_embedder(int width_in, int width_out, int num_classes, const std::string& module = "label_conditioner") {
         h->cdim = width_out;
-        h->lab_null = reg_f32("label_conditioner.null_classes_emb", width_in);
-        h->lab_emb = reg_f32("label_conditioner.label_emb.weight", (int64_t)num_classes * width_in);
-        h->lab_lnw = reg_f32("label_conditioner.class_to_cond.0.weight", width_in);
-        h->lab_lnb = reg_f32("label_conditioner.class_to_cond.0.bias", width_in);
-        h->lab_w1 = reg_f32("label_conditioner.class_to_cond.1.weight", (int64_t)width_out * width_in);
-        h->lab_b1 = reg_f32("label_conditioner.class_to_cond.1.bias", width_out);
-        h->lab_w2 = reg_f32("label_conditioner.class_to_cond.3.weight", (int64_t)width_out * width_out);
-        h->lab_b2 = reg_f32("label_conditioner.class_to_cond.3.bias", width_out);
+        h->lab_null = reg_f32(module + ".null_classes_emb", width_in);
+        h->lab_emb = reg_f32(module + ".label_emb.weight", (int64_t)num_classes * width_in);
+        h->lab_lnw = reg_f32(module + ".class_to_cond.0.weight", width_in);
+        h->lab_lnb = reg_f32(module + ".class_to_cond.0.bias", width_in);
+        h->lab_w1 = reg_f32(module + ".class_to_cond.1.weight", (int64_t)width_out * width_in);
+        h->lab_b1 = reg_f32(module + ".class_to_cond.1.bias", width_out);
+        h->lab_w2 = reg_f32(module + ".class_to_cond.3.weight", (int64_t)width_out * width_out);
+        h->lab_b2 = reg_f32(module + ".class_to_cond.3.bias", width_out);
     }
 };
 

@@ -1468,7 +1468,7 @@ __global__ void __launch_bounds__(256) class_embed_kernel(const long long* __res
                                                           const float* __restrict__ w1, const float* __restrict__ b1,
                                                           const float* __restrict__ w2, const float* __restrict__ b2, int ch, int cdim,
                                                           float* __restrict__ out, int nrows) {
-    __shared__ float e[512];
+    __shared__ float e[1024];
     __shared__ float hdn[2048];
     __shared__ float red[8];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -1507,7 +1507,7 @@ __global__ void __launch_bounds__(256) class_embed_kernel(const long long* __res
 const char* launch_class_embed(const long long* classes, int num_classes, int null_all, const float* emb, const float* null_emb,
                                const float* lnw, const float* lnb, const float* w1, const float* b1, const float* w2, const float* b2,
                                int ch, int cdim, float* out, int nrows, hipStream_t s) {
-    if (ch > 512 || cdim > 2048) return "class_embed: channels too large";
+    if (ch > 1024 || cdim > 2048) return "class_embed: channels too large";      // (e[] / hdn[] of the kernel)
     hipLaunchKernelGGL(class_embed_kernel, dim3(nrows), dim3(256), 0, s, classes, num_classes, null_all, emb, null_emb, lnw, lnb, w1, b1,
                        w2, b2, ch, cdim, out, nrows);
     return ADF_LAUNCH_CHECK("class_embed");

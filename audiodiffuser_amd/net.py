@@ -51,6 +51,9 @@ class NativeHandle:
         elif isinstance(cfg, UNet2dConfig):
             c = _lib.make_unet2d_config(cfg, _DTYPES[dtype])
             rc, what = self.lib.adf_unet2d_create(C.byref(c), C.byref(h)), "adf_unet2d_create"
+        elif getattr(cfg, "is_dit", False):         # audiodiffuser_amd.dit.DiTConfig (dit.py imports this module)
+            c = _lib.make_dit_config(cfg, _DTYPES[dtype])
+            rc, what = self.lib.adf_dit_create(C.byref(c), C.byref(h)), "adf_dit_create"
         else:
             c = _lib.make_config(cfg, _DTYPES[dtype], flags)
             rc, what = self.lib.adf_create(C.byref(c), C.byref(h)), "adf_create"
@@ -114,6 +117,10 @@ class NativeHandle:
     # ---- compute entry points (all tensors fp32, contiguous, on the handle's device) ----
     def _length(self, x: torch.Tensor) -> int:
         """The C ABI's length argument: L for [B, C, L]; H * W for the 2-D U-Net's [B, C, H, W] (after telling the handle the shape)."""
+        if getattr(self.cfg, "is_dit", False):      # DiT: [B, C, H, W], or [B, C, L] as H = 1 (dit.py:398-399)
+            hw = (int(x.shape[2]), int(x.shape[3])) if x.ndim == 4 else (1, int(x.shape[2]))
+            self.check(self.lib.adf_set_image_shape(self.h, hw[0], hw[1]), "adf_set_image_shape")
+            return hw[0] * hw[1]
         if x.ndim == 4:
             if not isinstance(self.cfg, (ADMConfig, UNet2dConfig)):
                 raise ValueError("a 4-D input needs the 2-D UNetModel")

@@ -23,6 +23,7 @@
  *                                     <- WaveNetNoise.forward (wavenet.py:169-180), adf_denoise / adf_sampler_run as above
  *   adf_unet2d_create              <- UNet2dBase.__init__ (src/models/backbones/unet2d.py:622-876); adf_net_forward on that handle
  *                                     <- UNet2dBase.forward (:879-972)
+ *   adf_dit_create                 <- DiT.__init__ (src/models/backbones/dit.py:282-326); adf_net_forward on that handle <- DiT.forward (:382-429)
  *
  * Conventions
  *   - every function returns 0 on success, non-zero on failure; adf_last_error() gives the message.
@@ -68,7 +69,8 @@ extern "C" {
  *    adf_sampler_desc, its kinds and adf_set_preconditioning are as they were.
  *    Added without a bump (new symbols only): adf_sampler_run_program and adf_sampler_program_nfe with adf_prog_desc / adf_prog_op and the ADF_PROG_*
  *    constants (VDPMSampler, VUniPCSampler).  adf_table_eval is reused as it is.  The table and the program are two public forms of one
- *    loop: the library lowers both to one internal op list and one driver runs it; neither form's structs, messages or cache keys depend on that. */
+ *    loop: the library lowers both to one internal op list and one driver runs it; neither form's structs, messages or cache keys depend on that.
+ *    Added without a bump (new symbols only): adf_dit_config and adf_dit_create (DiT); everything after create is the existing surface. */
 #define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
@@ -167,6 +169,19 @@ typedef struct adf_unet2d_config {
     int32_t dtype;                          /* ADF_DTYPE_F32 only */
 } adf_unet2d_config;
 
+/* Hyper-parameters of DiT, the adaLN-Zero diffusion transformer (dit.py:282-300), as the device runs it: label or no conditioning, the plain
+ * attention branch (no text context, no RoPE, no qk-l2norm).  mlp_hidden = int(hidden_size * mlp_ratio), what Mlp is built with (dit.py:238). */
+typedef struct adf_dit_config {
+    int32_t input_h, input_w;               /* input_size: the only (H, W) the net takes (PatchEmbed's strict_img_size); [B][C][L] inputs are H = 1 */
+    int32_t patch_h, patch_w;               /* patch_size: divides input_size; patch_h * patch_w * in_channels in [4, 256] */
+    int32_t in_channels;                    /* = out_channels */
+    int32_t hidden_size;                    /* a multiple of 64, at most 1024 */
+    int32_t depth, num_heads;               /* hidden_size / num_heads = 32 or 64 */
+    int32_t mlp_hidden;                     /* a multiple of 32, at most 4096 */
+    int32_t num_classes;                    /* 0 = unconditional; > 0: y_embedder (LabelEmbedder) + adf_set_condition (labels, guidance) */
+    int32_t dtype;                          /* ADF_DTYPE_F32 only */
+} adf_dit_config;
+
 typedef struct adf_handle adf_handle;
 
 int adf_create(const adf_net_config* cfg, adf_handle** out);
@@ -182,6 +197,16 @@ int adf_adm_create(const adf_adm_config* cfg, adf_handle** out);
  * forward(x, time = c_noise), optionally class-conditional (adf_set_condition).  Debug taps: "init_conv", "init_resnet_block", "downs.<i>",
  * "mid_block", "ups.<i>", "final_res_block" (the module outputs the reference's fixtures hold) and every stored intermediate. */
 int adf_unet2d_create(const adf_unet2d_config* cfg, adf_handle** out);
+/* A DiT handle (added without a version bump: new symbols only): the same 2-D conventions (adf_set_image_shape first, with exactly input_size; a
+ * [B][C][L] input is H = 1, W = L).  forward(x, t = c_noise), optionally class-conditional (adf_set_condition; the label embedding joins the time
+ * embedding before every adaLN modulation).  State-dict keys: pos_embed, x_embedder.proj.*, t_embedder.mlp.{0,2}.*, y_embedder.* (num_classes > 0),
+ * blocks.<i>.attn.{to_q,to_kv,to_context,to_out}.weight (to_context is loaded and never read), blocks.<i>.mlp.{fc1,fc2}.*,
+ * blocks.<i>.adaLN_modulation.1.*, final_layer.{linear,adaLN_modulation.1}.*.  Exact fp32: every Linear on v_mfma_f32_32x32x2_f32.  The last kernel
+ * has all three epilogues (raw, clamped, unclipped), so every preconditioning kind is one pass.  Debug taps ([B][D][T] as adf_debug_tap_copy lays
+ * them out): "x_embedder", "c" ([B][D][1]), "blocks.<i>", "blocks.<i>.attn" / "blocks.<i>.mlp" (the branches before their gates), "final_layer"
+ * (before unpatchify); the per-block taps exist while 3 * depth * B * T * D floats fit 512 MiB (beyond that, or with the route switch ADF_DIT_TAPS=0 in the
+ * environment at create, the residual stream is updated in place and they are not kept). */
+int adf_dit_create(const adf_dit_config* cfg, adf_handle** out);
 int adf_set_image_shape(adf_handle* h, int H, int W);
 
 /* Clipping of every denoiser evaluation from here on (adf_denoise, adf_sampler_run): 0 = clamp to [-1, 1] (the default), q in (0, 1] = the dynamic
