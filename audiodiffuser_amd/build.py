@@ -15,7 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libadf_hip.so")
 SOURCES = ["adf_gemm.hip", "adf_kernels.hip", "adf_wavenet.hip", "adf_conv2d.hip", "adf_api.hip", "adf_net_unet1d.hip", "adf_net_wavenet.hip",
-           "adf_net_adm.hip", "adf_unet2d.hip", "adf_net_unet2d.hip", "adf_dit.hip", "adf_net_dit.hip", "adf_sampler.hip", "adf_bench_replay.hip", "adf_istft.hip", "adf_stft.hip", "adf_loss.hip"]
+           "adf_net_adm.hip", "adf_unet2d.hip", "adf_net_unet2d.hip", "adf_dit.hip", "adf_dit_x3.hip", "adf_net_dit.hip", "adf_sampler.hip", "adf_bench_replay.hip", "adf_istft.hip", "adf_stft.hip", "adf_loss.hip"]
 # adf_gemm.hip: the SLP vectoriser would pair the prologue arithmetic that adf_gemm_pp.h places one element per MFMA gap
 # into v_pk_* operations (which are slower beside MFMAs and land in one gap instead of two)
 # adf_loss.hip: its fp32 operations are each rounded on their own (bit-equal to the reference's separate tensor ops); the default, -ffp-contract=fast,

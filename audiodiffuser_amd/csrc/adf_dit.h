@@ -9,6 +9,8 @@
 //   launch_dit_patch_embed   PatchEmbed (conv with stride = kernel = patch) of c_in x, + bias + pos_embed
 //   launch_dit_unpatchify    nhwpqc -> nchpwq scatter of final_layer.linear's rows with the three FwdIO epilogue modes
 //   launch_dit_cond          c = time embedding (+ label embedding); SiLU(c), the input of every adaLN_modulation
+//   launch_dit_linear_x3, launch_dit_attention_x3, launch_dit_split_weight
+//                            the split-bf16 (f32x3) mode's token linear and key-tiled self-attention (below)
 #pragma once
 #include "adf_common.h"
 
@@ -32,6 +34,18 @@ struct DitLinearArgs {
     float* pre = nullptr;           // kDitEpiGate: where given, acc + bias is also stored here ([M][N]: the branch before its gate, a debug tap)
 };
 const char* launch_dit_linear(const DitLinearArgs& a, hipStream_t s);
+
+// ---- split-bf16 (f32x3) mode (adf_dit_x3.hip; the mode: adf_common.h) -- fp32 tensors in and out, matrix-core operands as bf16 hi + lo, three
+// v_mfma_f32_32x32x16_bf16 per product (lo hi + hi lo + hi hi)
+constexpr int kDitX3TileK = 32;
+// fp32 [numel] -> bf16 hi and lo planes [numel]; numel a multiple of 4.  Run once per (re)load on the padded weight buffer: padding rows stay zero.
+const char* launch_dit_split_weight(const float* w, unsigned short* hi, unsigned short* lo, long long numel, hipStream_t s);
+// launch_dit_linear on split operands: a.w is not read, the weight comes as the planes [round_up(N, 128)][K] of launch_dit_split_weight; K a
+// multiple of 32; the activation is split inside the kernel.  Same epilogues, same guards (res == y allowed).
+const char* launch_dit_linear_x3(const DitLinearArgs& a, const unsigned short* w_hi, const unsigned short* w_lo, hipStream_t s);
+// out[b][n][h D + :] = softmax(q k^T / sqrt(D)) v per (sample, head) on qkv rows [B N][3 C] (q | k | v blocks of C = heads D floats), head dim D 32
+// or 64, any N >= 1: key tiles of 64 with an online softmax
+const char* launch_dit_attention_x3(const float* qkv, float* out, int B, int N, int C, int heads, hipStream_t s);
 
 // y[r][:] = (x[r][:] - mean) / sqrt(var + 1e-6) * (1 + scale[b][:]) + shift[b][:], b = r / T; shift / scale rows are mod_bstride floats apart.
 // D a multiple of 4, at most 1024.

@@ -1,5 +1,6 @@
 // DiT, the adaLN-Zero diffusion transformer, behind the C ABI (reference: src/models/backbones/dit.py:278-429): adf_dit_create, registry and the walk.
-// Exact fp32 on token-major activations [B][T][D]; kernels: adf_dit.h, attention: launch_attention (adf_kernels.h).
+// Token-major fp32 activations [B][T][D]; kernels: adf_dit.h, attention: launch_attention (adf_kernels.h).  ADF_DTYPE_F32: exact fp32.
+// ADF_DTYPE_F32X3: the four token linears of a block and its attention take the split-bf16 kernels (adf_dit_x3.hip); everything else is the fp32 path.
 #include "adf_api_internal.h"
 #include "adf_dit.h"
 
@@ -11,7 +12,14 @@ namespace adf_api {
 // Linear weights stay the state dict's [N][K] rows (both GEMM operands are K-contiguous), padded with zero rows to whole 128-row tiles: the
 // kernel's weight staging loads are unguarded (adf_dit.h).  to_q and to_kv share one [3 D][D] buffer; every adaLN_modulation of the net shares
 // adf_handle::film_w / film_b ([(6 depth + 2) D][D]), so that one launch projects all of them.
-struct DitBlock { float *wqkv = nullptr, *wout = nullptr, *fc1w = nullptr, *fc1b = nullptr, *fc2w = nullptr, *fc2b = nullptr; int mod_off = 0; };
+// f32x3: a linear's weight is also kept as bf16 hi and lo planes of the padded shape (X3W), split from the fp32 buffer -- which stays the load target --
+// before the first pass after a (re)load (DitNet::prepare).
+struct X3W { unsigned short *hi = nullptr, *lo = nullptr; long long numel = 0; };
+struct DitBlock {
+    float *wqkv = nullptr, *wout = nullptr, *fc1w = nullptr, *fc1b = nullptr, *fc2w = nullptr, *fc2b = nullptr;
+    X3W xqkv, xout, xfc1, xfc2;
+    int mod_off = 0;
+};
 
 struct DitNet : Net {
     adf_dit_config cfg;
@@ -20,10 +28,15 @@ struct DitNet : Net {
     float *fin_w = nullptr, *fin_b = nullptr;
     int fin_mod_off = 0;
     bool block_taps = true;              // route switch ADF_DIT_TAPS (read at create): 0 = never keep the per-block taps, i.e. always the in-place residual stream
+    // route switches of the f32x3 mode (read at create): ADF_DIT_X3_LINEAR=0 keeps dit_linear_kernel, ADF_DIT_X3_ATT=0 keeps launch_attention(.., 0, ..)
+    bool x3_linear = false, x3_att = false;
+    bool split_done = false;             // the hi / lo planes match the fp32 weights
     std::vector<DitBlock> blocks;
 
     DitNet() { class_in_temb = true; image = true; unclipped_epilogue = true; }
     int build_weights(adf_handle* h) override;
+    void weight_loaded() override { split_done = false; }
+    int prepare(adf_handle* h, hipStream_t s) override;
     int check_image(adf_handle* h, int L) override {
         if (H != cfg.input_h || W != cfg.input_w || (long long)H * W != L)
             return fail(h, "DiT: call adf_set_image_shape(H, W) with the net's input_size (" + std::to_string(cfg.input_h) + ", " +
@@ -47,6 +60,13 @@ int DitNet::build_weights(adf_handle* h) {
     float* ctx = (float*)dalloc(h, (size_t)2 * D * D * 4);
     if (!h->film_w || !h->film_b || !ctx) return fail(h, "device allocation failed while building the weight registry");
     auto padded = [&](int n, int k) { float* q = (float*)dalloc(h, (size_t)round_up(n, kDitTileN) * k * 4); if (!q) R.ok = false; return q; };
+    auto planes = [&](int n, int k) {
+        X3W x;
+        x.numel = (long long)round_up(n, kDitTileN) * k;
+        x.hi = (unsigned short*)dalloc(h, (size_t)x.numel * 2); x.lo = (unsigned short*)dalloc(h, (size_t)x.numel * 2);
+        if (!x.hi || !x.lo) R.ok = false;
+        return x;
+    };
     // nn.Module.state_dict order: the module's own parameter (pos_embed) before its children
     pos = R.reg_f32("pos_embed", (int64_t)T * D);
     pe_w = R.reg_f32("x_embedder.proj.weight", (int64_t)D * cfg.in_channels * cfg.patch_h * cfg.patch_w);
@@ -62,6 +82,7 @@ int DitNet::build_weights(adf_handle* h) {
         const std::string pre = "blocks." + std::to_string(i);
         b.mod_off = 6 * D * i;
         b.wqkv = padded(3 * D, D); b.wout = padded(D, D); b.fc1w = padded(hid, D); b.fc2w = padded(D, hid);
+        if (x3_linear) { b.xqkv = planes(3 * D, D); b.xout = planes(D, D); b.xfc1 = planes(hid, D); b.xfc2 = planes(D, hid); }
         if (!R.ok) break;
         R.reg_f32(pre + ".attn.to_q.weight", (int64_t)D * D, b.wqkv);
         R.reg_f32(pre + ".attn.to_kv.weight", (int64_t)2 * D * D, b.wqkv + (size_t)D * D);
@@ -85,6 +106,18 @@ int DitNet::build_weights(adf_handle* h) {
     return R.ok ? 0 : fail(h, "device allocation failed while building the weight registry");
 }
 
+// f32x3: the hi / lo planes of every block linear from the fp32 buffers (stream-ordered behind the loads)
+int DitNet::prepare(adf_handle* h, hipStream_t s) {
+    if (!x3_linear || split_done) return 0;
+    for (const DitBlock& b : blocks) {
+        const std::pair<const float*, const X3W*> ws[4] = {{b.wqkv, &b.xqkv}, {b.wout, &b.xout}, {b.fc1w, &b.xfc1}, {b.fc2w, &b.xfc2}};
+        for (const auto& w : ws)
+            if (const char* e = launch_dit_split_weight(w.first, w.second->hi, w.second->lo, w.second->numel, s)) return fail(h, e);
+    }
+    split_done = true;
+    return 0;
+}
+
 // DiT.forward (dit.py:382-429); x / out are the reference's [B][C][H][W] fp32 (H = 1 for the [B][C][L] form)
 int DitNet::forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
     Walker W{h, p, s};
@@ -92,11 +125,11 @@ int DitNet::forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
     const int B = p->B, M = B * T, depth = cfg.depth;
     auto falloc = [&](size_t n) { return (float*)W.alloc(n * 4); };
     auto linear = [&](const float* x, const float* w, const float* bias, float* y, int m, int n, int k, int epi, const float* res, const float* gate,
-                      int gate_bs, float* pre = nullptr) {
+                      int gate_bs, float* pre = nullptr, const X3W* xw = nullptr) {
         if (!W.live()) return;
         DitLinearArgs a;
         a.x = x; a.w = w; a.bias = bias; a.y = y; a.M = m; a.N = n; a.K = k; a.epi = epi; a.res = res; a.gate = gate; a.gate_bstride = gate_bs; a.T = T; a.pre = pre;
-        W.check(launch_dit_linear(a, s));
+        W.check(xw && x3_linear ? launch_dit_linear_x3(a, xw->hi, xw->lo, s) : launch_dit_linear(a, s));
     };
     // ---- c = t_embedder(t) (+ y_embedder(classes)), then every adaLN_modulation in one GEMM; an unconditional sampler run brings the rows of this
     // evaluation already projected (film_pre: Plan::film_all, filled at the head of the run)
@@ -141,18 +174,18 @@ int DitNet::forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) {
         const std::string bn = "blocks." + std::to_string(i);
         const float* m6 = mod + b.mod_off;          // shift_msa | scale_msa | gate_msa | shift_mlp | scale_mlp | gate_mlp (dit.py:251)
         if (W.live()) W.check(launch_dit_ln_modulate(x, xn, m6, m6 + D, mod_bs, M, T, D, s));
-        linear(xn, b.wqkv, nullptr, qkv, M, 3 * D, D, kDitEpiBias, nullptr, nullptr, 0);
+        linear(xn, b.wqkv, nullptr, qkv, M, 3 * D, D, kDitEpiBias, nullptr, nullptr, 0, nullptr, &b.xqkv);
         // Attention's plain branch (attention_utils.py:157-184): softmax(q k^T / sqrt(head dim)) v on q | k | v blocks
-        if (W.live()) W.check(launch_attention(qkv, att, 0, B, T, D, cfg.num_heads, s));
+        if (W.live()) W.check(x3_att ? launch_dit_attention_x3(qkv, att, B, T, D, cfg.num_heads, s) : launch_attention(qkv, att, 0, B, T, D, cfg.num_heads, s));
         float* xm = keep ? xmid : xres;
         float* xo = keep ? falloc((size_t)M * D) : xres;
         float* ab = keep ? falloc((size_t)M * D) : nullptr;                 // the attention branch before its gate
-        linear(att, b.wout, nullptr, xm, M, D, D, kDitEpiGate, x, m6 + 2 * D, mod_bs, ab);
+        linear(att, b.wout, nullptr, xm, M, D, D, kDitEpiGate, x, m6 + 2 * D, mod_bs, ab, &b.xout);
         if (keep) W.tap(bn + ".attn", Act{ab, D, T});
         if (W.live()) W.check(launch_dit_ln_modulate(xm, xn, m6 + 3 * D, m6 + 4 * D, mod_bs, M, T, D, s));
-        linear(xn, b.fc1w, b.fc1b, hb, M, hid, D, kDitEpiGelu, nullptr, nullptr, 0);
+        linear(xn, b.fc1w, b.fc1b, hb, M, hid, D, kDitEpiGelu, nullptr, nullptr, 0, nullptr, &b.xfc1);
         float* mb = keep ? falloc((size_t)M * D) : nullptr;
-        linear(hb, b.fc2w, b.fc2b, xo, M, D, hid, kDitEpiGate, xm, m6 + 5 * D, mod_bs, mb);
+        linear(hb, b.fc2w, b.fc2b, xo, M, D, hid, kDitEpiGate, xm, m6 + 5 * D, mod_bs, mb, &b.xfc2);
         if (keep) W.tap(bn + ".mlp", Act{mb, D, T});
         x = xo;
         if (keep) W.tap(bn, Act{x, D, T});
@@ -175,7 +208,7 @@ extern "C" int adf_dit_create(const adf_dit_config* cfg, adf_handle** out) {
     if (create_begin("adf_dit_create", cfg, out)) return 1;
     const adf_dit_config& c = *cfg;
     auto bad = [&](const char* m) { g_create_error = std::string("adf_dit_create: ") + m; return 1; };
-    if (c.dtype != ADF_DTYPE_F32) return bad("dtype must be ADF_DTYPE_F32 (DiT runs in exact fp32 only)");
+    if (c.dtype != ADF_DTYPE_F32 && c.dtype != ADF_DTYPE_F32X3) return bad("dtype must be ADF_DTYPE_F32 or ADF_DTYPE_F32X3 (no bf16-storage DiT)");
     if (c.input_h < 1 || c.input_w < 1 || c.patch_h < 1 || c.patch_w < 1 || c.input_h % c.patch_h || c.input_w % c.patch_w)
         return bad("input_size must be positive and divisible by patch_size");
     if (c.in_channels < 1 || (long long)c.in_channels * c.patch_h * c.patch_w < 4 || (long long)c.in_channels * c.patch_h * c.patch_w > 256)
@@ -191,6 +224,8 @@ extern "C" int adf_dit_create(const adf_dit_config* cfg, adf_handle** out) {
     auto net = std::make_unique<DitNet>();
     net->cfg = c;
     net->block_taps = adf_route_switch("ADF_DIT_TAPS", 1) != 0;
+    net->x3_linear = c.dtype == ADF_DTYPE_F32X3 && adf_route_switch("ADF_DIT_X3_LINEAR", 1) != 0;
+    net->x3_att = c.dtype == ADF_DTYPE_F32X3 && adf_route_switch("ADF_DIT_X3_ATT", 1) != 0;
     net->D = c.hidden_size; net->T = (int)tokens; net->hid = c.mlp_hidden; net->nout = c.patch_h * c.patch_w * c.in_channels;
     NetDims& d = net->dims;
     d.in_channels = d.out_channels = c.in_channels;

@@ -3,7 +3,8 @@
 
 Contract kept: the constructor kwargs and defaults (hydra ``_target_`` instantiation), ``state_dict()`` keys / order / shapes (reference checkpoints
 strict-load; ``attn.to_context`` is loaded and never read), ``forward(x, t, classes=None, text_embeds=None, text_mask=None, cond_drop_prob=None)``
-on ``[B, C, H, W]`` with ``(H, W) == input_size`` or ``[B, C, L]`` (the same call with ``H = 1``).  On the device, in exact fp32: unconditional nets and
+on ``[B, C, H, W]`` with ``(H, W) == input_size`` or ``[B, C, L]`` (the same call with ``H = 1``).  On the device, in exact fp32 or in the split-bf16
+mode (``compute_dtype="f32x3"``: fp32 storage, bf16 hi + lo GEMM and attention operands): unconditional nets and
 ``label_cond=True`` with ``num_classes``; the attention's plain branch (no text context, so no RoPE and no mask).  Every other branch raises, naming
 its argument.
 """
@@ -184,7 +185,9 @@ def _init_like_reference(name: str, shape, kind: str, cfg: DiTConfig) -> torch.T
 
 
 class DiT(HipNet):
-    """HIP-backed ``DiT``.  Extra kwarg: ``compute_dtype``, "fp32" only.  Served widths: ``hidden_size`` a multiple of 64 up to 1024, head dim 32 or
+    """HIP-backed ``DiT``.  Extra kwarg: ``compute_dtype`` in {"fp32", "f32x3"}: "fp32" (default) is exact fp32; "f32x3" keeps fp32 storage and every
+    non-GEMM kernel and runs the q|k|v, to_out, fc1 and fc2 linears and the attention products on the bf16 matrix cores with every operand split into
+    bf16 hi + lo (three MFMAs per product, ~1e-5 of exact fp32).  Both modes serve the same widths: ``hidden_size`` a multiple of 64 up to 1024, head dim 32 or
     64, ``int(hidden_size * mlp_ratio)`` a multiple of 32 up to 4096, ``prod(patch_size) * in_channels`` in [4, 256], any token count
     (DiT-S, DiT-B and DiT-L; DiT-XL's head dim 72 is refused)."""
 
@@ -192,8 +195,9 @@ class DiT(HipNet):
                  cond_drop_prob=0.1, num_classes=None, class_embed_dim=None, label_cond=False, text_cond=False, text_embed_dim=512,
                  max_text_len=128, use_self_text_cond=True, use_qk_l2norm=False, compute_dtype: str = "fp32"):
         super().__init__()
-        if compute_dtype != "fp32":
-            raise ValueError(f"compute_dtype={compute_dtype!r}: DiT runs in exact fp32 only ('fp32')")
+        if compute_dtype not in ("fp32", "f32x3"):
+            raise ValueError(f"compute_dtype={compute_dtype!r}: DiT runs in 'fp32' (exact) or 'f32x3' (split-bf16 GEMM operands, fp32 storage); "
+                             "there is no bf16-storage DiT")
         if text_cond:
             raise NotImplementedError("DiT(text_cond=True) is not on the device path (text conditioning, and with it RoPE and the key mask)")
         if class_embed_dim is not None:

@@ -27,7 +27,7 @@ from .unet2d_config import UNet2dConfig
 from .weights import param_specs
 
 _DTYPES = {"fp32": _lib.DTYPE_F32, "float32": _lib.DTYPE_F32, "bf16": _lib.DTYPE_BF16, "bfloat16": _lib.DTYPE_BF16,
-           "f32x3": _lib.DTYPE_F32X3}      # split-bf16 (UNet1dBase and UNetModel only): fp32 storage, bf16 hi + lo operands, 3 MFMAs per product
+           "f32x3": _lib.DTYPE_F32X3}      # split-bf16 (UNet1dBase, UNetModel and DiT only): fp32 storage, bf16 hi + lo operands, 3 MFMAs per product
 
 
 def _stream_ptr(device: torch.device) -> int:

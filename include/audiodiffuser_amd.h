@@ -78,7 +78,7 @@ int adf_abi_version(void);
 
 #define ADF_DTYPE_F32 0  /* parity mode: fp32 storage, exact-fp32 MFMA */
 #define ADF_DTYPE_BF16 1 /* throughput mode: bf16 storage, fp32 accumulate */
-#define ADF_DTYPE_F32X3 2 /* split-bf16 mode (UNet1dBase and the ADM UNetModel): fp32 storage as ADF_DTYPE_F32; a GEMM operand x is staged as bf16 hi = rn(x) and
+#define ADF_DTYPE_F32X3 2 /* split-bf16 mode (UNet1dBase, the ADM UNetModel and DiT): fp32 storage as ADF_DTYPE_F32; a GEMM operand x is staged as bf16 hi = rn(x) and
                              lo = rn(x - hi) (x = hi + lo to 2^-17) and a product is hi*hi + hi*lo + lo*hi on the bf16 MFMA with fp32 accumulation:
                              ~1e-5 relative per layer against the exact-fp32 mode, inside the 1e-3 bar of the reference comparison, at the bf16 MFMA rate / 3 */
 
@@ -179,7 +179,7 @@ typedef struct adf_dit_config {
     int32_t depth, num_heads;               /* hidden_size / num_heads = 32 or 64 */
     int32_t mlp_hidden;                     /* a multiple of 32, at most 4096 */
     int32_t num_classes;                    /* 0 = unconditional; > 0: y_embedder (LabelEmbedder) + adf_set_condition (labels, guidance) */
-    int32_t dtype;                          /* ADF_DTYPE_F32 only */
+    int32_t dtype;                          /* ADF_DTYPE_F32 or ADF_DTYPE_F32X3 */
 } adf_dit_config;
 
 typedef struct adf_handle adf_handle;
@@ -201,7 +201,12 @@ int adf_unet2d_create(const adf_unet2d_config* cfg, adf_handle** out);
  * [B][C][L] input is H = 1, W = L).  forward(x, t = c_noise), optionally class-conditional (adf_set_condition; the label embedding joins the time
  * embedding before every adaLN modulation).  State-dict keys: pos_embed, x_embedder.proj.*, t_embedder.mlp.{0,2}.*, y_embedder.* (num_classes > 0),
  * blocks.<i>.attn.{to_q,to_kv,to_context,to_out}.weight (to_context is loaded and never read), blocks.<i>.mlp.{fc1,fc2}.*,
- * blocks.<i>.adaLN_modulation.1.*, final_layer.{linear,adaLN_modulation.1}.*.  Exact fp32: every Linear on v_mfma_f32_32x32x2_f32.  The last kernel
+ * blocks.<i>.adaLN_modulation.1.*, final_layer.{linear,adaLN_modulation.1}.*.  ADF_DTYPE_F32: exact fp32, every Linear on v_mfma_f32_32x32x2_f32.
+ * ADF_DTYPE_F32X3 (additive, no version bump; the same widths): the q|k|v projection, to_out, fc1 and fc2 of every block and its attention (Q K^T and
+ * P V, key-tiled, any token count) take bf16 hi + lo operands, three bf16 MFMAs per product; the modulation GEMM, final_layer.linear and everything
+ * that is not a GEMM stay the fp32 kernels.  The fp32 weight buffers stay the load target; the hi / lo planes are rebuilt before the first pass after
+ * a load.  Route switches read from the environment at create (default 1): ADF_DIT_X3_LINEAR=0 keeps the fp32 token linear, ADF_DIT_X3_ATT=0 the fp32
+ * vector attention in an ADF_DTYPE_F32X3 handle (both 0: bit for bit the ADF_DTYPE_F32 handle).  ADF_DTYPE_BF16 is refused.  The last kernel
  * has all three epilogues (raw, clamped, unclipped), so every preconditioning kind is one pass.  Debug taps ([B][D][T] as adf_debug_tap_copy lays
  * them out): "x_embedder", "c" ([B][D][1]), "blocks.<i>", "blocks.<i>.attn" / "blocks.<i>.mlp" (the branches before their gates), "final_layer"
  * (before unpatchify); the per-block taps exist while 3 * depth * B * T * D floats fit 512 MiB (beyond that, or with the route switch ADF_DIT_TAPS=0 in the

@@ -6,7 +6,10 @@
 The arms alternate after two warm-up rounds; the figure of an arm is the median of its R runs.  The two results are compared first (the block taps are
 not kept at this size, so this is also the check of the in-place residual path).  ``tf_whole_pass`` counts the GEMM and attention FLOPs of the pass; the
 per-kernel shares (profiles/README.md) come from one ``rocprofv3 --kernel-trace --stats`` run of this script.
-Usage: dit_pass.py [B] [repeats] [depth]; prints one JSON line."""
+With the optional fourth argument ``f32x3`` a third arm, ``hip_f32x3`` -- the same net with ``compute_dtype="f32x3"`` (split-bf16 linears and
+attention), driven like ``hip`` -- alternates with the other two in the same process, and the line gains ``rel_f32x3_vs_torch``,
+``f32x3_over_torch`` and ``f32x3_over_fp32``; without it the run and its keys are as before.
+Usage: dit_pass.py [B] [repeats] [depth] [f32x3]; prints one JSON line."""
 import argparse, json, math, os, sys
 import torch
 import torch.nn.functional as F
@@ -18,6 +21,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("B", nargs="?", type=int, default=16)
 ap.add_argument("R", nargs="?", type=int, default=9)
 ap.add_argument("depth", nargs="?", type=int, default=12)
+ap.add_argument("compute_dtype", nargs="?", choices=["fp32", "f32x3"], default="fp32")
 args = ap.parse_args()
 B, R, H, W, C = args.B, args.R, 256, 128, 2
 kw = dict(input_size=[H, W], patch_size=[8, 4], in_channels=C, hidden_size=768, depth=args.depth, num_heads=12, mlp_ratio=4.0)
@@ -26,6 +30,11 @@ net = A.DiT(**kw)
 w = generate_weights(net.cfg, seed=7)
 net.load_state_dict(w, strict=True)
 net = net.to(dev)
+net3 = None
+if args.compute_dtype == "f32x3":
+    net3 = A.DiT(compute_dtype="f32x3", **kw)
+    net3.load_state_dict(w, strict=True)
+    net3 = net3.to(dev)
 wd = {k: v.to(dev) for k, v in w.items()}
 D, heads, (p1, p2) = 768, 12, (8, 4)
 gh, gw = H // p1, W // p2
@@ -66,6 +75,7 @@ with torch.no_grad():
     y_ref = torch_forward(x, tt)
     torch.cuda.synchronize()
     rel = float((y_hip - y_ref).abs().max() / y_ref.abs().max())
+    rel3 = float((net3(x, tt) - y_ref).abs().max() / y_ref.abs().max()) if net3 is not None else None
     # the graph-replayed arms: x_next = x + (0 - 1) v at t = 1 for the library, the bare forward for torch
     rf, flow, lin = A.ReflowEulerSampler(num_steps=1, use_heun=False, use_graph=True), A.ReFlow(), A.LinearSchedule(1.0, 0.0, 2)()
     side = torch.cuda.Stream()
@@ -78,6 +88,8 @@ with torch.no_grad():
     with torch.cuda.graph(graph):
         y_g = torch_forward(x, tt)
     arms = {"hip": lambda: rf(x, fn=flow.denoise_fn, net=net, sigmas=lin), "torch": lambda: graph.replay()}
+    if net3 is not None:
+        arms["hip_f32x3"] = lambda: rf(x, fn=flow.denoise_fn, net=net3, sigmas=lin)
     ms = {k: [] for k in arms}
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     for _ in range(2):
@@ -94,8 +106,12 @@ with torch.no_grad():
 med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
 M, hid = B * T, 4 * D
 flops = args.depth * (2.0 * M * D * 3 * D + 2.0 * M * D * D + 4.0 * M * D * hid + 4.0 * B * heads * T * T * (D // heads))
-print(json.dumps({"net": f"DiT-B widths (768 / 12 heads / depth {args.depth} / ratio 4), unconditional, fp32", "shape": [B, C, H, W], "tokens": T,
-                  "rel_hip_vs_torch": rel, "ms_median": {k: round(v, 3) for k, v in med.items()},
-                  "ms_all": {k: [round(u, 3) for u in v] for k, v in ms.items()}, "pass_gflop": round(flops / 1e9, 1),
-                  "tf_whole_pass": {k: round(flops / (v * 1e-3) / 1e12, 1) for k, v in med.items()},
-                  "hip_over_torch": round(med["hip"] / med["torch"], 3)}))
+res = {"net": f"DiT-B widths (768 / 12 heads / depth {args.depth} / ratio 4), unconditional, fp32", "shape": [B, C, H, W], "tokens": T,
+       "rel_hip_vs_torch": rel, "ms_median": {k: round(v, 3) for k, v in med.items()},
+       "ms_all": {k: [round(u, 3) for u in v] for k, v in ms.items()}, "pass_gflop": round(flops / 1e9, 1),
+       "tf_whole_pass": {k: round(flops / (v * 1e-3) / 1e12, 1) for k, v in med.items()},
+       "hip_over_torch": round(med["hip"] / med["torch"], 3)}
+if net3 is not None:
+    res.update({"rel_f32x3_vs_torch": rel3, "f32x3_over_torch": round(med["hip_f32x3"] / med["torch"], 3),
+                "f32x3_over_fp32": round(med["hip_f32x3"] / med["hip"], 3)})
+print(json.dumps(res))
