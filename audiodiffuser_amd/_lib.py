@@ -135,6 +135,17 @@ class AdfDitConfig(C.Structure):
                 ("dtype", C.c_int32)]
 
 
+ADF_DAC_MAX_RATES, ADF_DAC_MAX_WIDTHS = 6, 8
+DAC_KIND_DECODER, DAC_KIND_AUTOENCODER = 0, 1
+
+
+class AdfDacConfig(C.Structure):
+    """``adf_dac_config`` of include/audiodiffuser_amd.h."""
+    _fields_ = [("kind", C.c_int32), ("input_channel", C.c_int32), ("channels", C.c_int32), ("n_rates", C.c_int32),
+                ("rates", C.c_int32 * ADF_DAC_MAX_RATES), ("d_out", C.c_int32), ("n_widths", C.c_int32), ("widths", C.c_int32 * ADF_DAC_MAX_WIDTHS),
+                ("dtype", C.c_int32)]
+
+
 class AdfRunCounters(C.Structure):
     """``adf_run_counters`` of include/audiodiffuser_amd.h."""
     _fields_ = [("sampler_runs", C.c_int64), ("sampler_evals", C.c_int64), ("graph_captures", C.c_int64),
@@ -163,6 +174,9 @@ EXPORTS = {
     "adf_adm_create": (C.c_int, [C.POINTER(AdfAdmConfig), C.POINTER(C.c_void_p)]),
     "adf_unet2d_create": (C.c_int, [C.POINTER(AdfUNet2dConfig), C.POINTER(C.c_void_p)]),
     "adf_dit_create": (C.c_int, [C.POINTER(AdfDitConfig), C.POINTER(C.c_void_p)]),
+    "adf_dac_create": (C.c_int, [C.POINTER(AdfDacConfig), C.POINTER(C.c_void_p)]),
+    "adf_dac_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "adf_dac_output_length": (C.c_int64, [C.c_void_p, C.c_int]),
     "adf_set_image_shape": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "adf_set_dynamic_threshold": (C.c_int, [C.c_void_p, C.c_float]),
     "adf_set_preconditioning": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]),

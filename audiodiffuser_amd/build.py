@@ -15,13 +15,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libadf_hip.so")
 SOURCES = ["adf_gemm.hip", "adf_kernels.hip", "adf_wavenet.hip", "adf_conv2d.hip", "adf_api.hip", "adf_net_unet1d.hip", "adf_net_wavenet.hip",
-           "adf_net_adm.hip", "adf_unet2d.hip", "adf_net_unet2d.hip", "adf_dit.hip", "adf_dit_x3.hip", "adf_net_dit.hip", "adf_sampler.hip", "adf_bench_replay.hip", "adf_istft.hip", "adf_stft.hip", "adf_loss.hip"]
+           "adf_net_adm.hip", "adf_unet2d.hip", "adf_net_unet2d.hip", "adf_dit.hip", "adf_dit_x3.hip", "adf_net_dit.hip", "adf_dac.hip", "adf_net_dac.hip", "adf_sampler.hip", "adf_bench_replay.hip", "adf_istft.hip", "adf_stft.hip", "adf_loss.hip"]
 # adf_gemm.hip: the SLP vectoriser would pair the prologue arithmetic that adf_gemm_pp.h places one element per MFMA gap
 # into v_pk_* operations (which are slower beside MFMAs and land in one gap instead of two)
 # adf_loss.hip: its fp32 operations are each rounded on their own (bit-equal to the reference's separate tensor ops); the default, -ffp-contract=fast,
 # fuses a product and a sum into an FMA even where they are written with __fmul_rn / __fadd_rn
 EXTRA_FLAGS = {"adf_gemm.hip": ["-fno-slp-vectorize"], "adf_loss.hip": ["-ffp-contract=off"]}
-HEADERS = ["adf_common.h", "adf_gemm.h", "adf_gemm_pp.h", "adf_gemm_rb.h", "adf_gemm_rbx3.h", "adf_gemm_up.h", "adf_kernels.h", "adf_wavenet.h", "adf_conv2d.h", "adf_unet2d.h", "adf_dit.h", "adf_transformer.h", "adf_resblock_small.h", "adf_resblock_split.h", "adf_api_internal.h", "adf_net_wavenet.h", "adf_walk2d.h", "adf_istft.h", "adf_stft.h", "adf_spectral_host.h", "adf_loss.h", os.path.join("..", "..", "include", "audiodiffuser_amd.h")]
+HEADERS = ["adf_common.h", "adf_gemm.h", "adf_gemm_pp.h", "adf_gemm_rb.h", "adf_gemm_rbx3.h", "adf_gemm_up.h", "adf_kernels.h", "adf_wavenet.h", "adf_conv2d.h", "adf_unet2d.h", "adf_dit.h", "adf_dac.h", "adf_transformer.h", "adf_resblock_small.h", "adf_resblock_split.h", "adf_api_internal.h", "adf_net_wavenet.h", "adf_walk2d.h", "adf_istft.h", "adf_stft.h", "adf_spectral_host.h", "adf_loss.h", os.path.join("..", "..", "include", "audiodiffuser_amd.h")]
 ARCH = "gfx950"
 
 

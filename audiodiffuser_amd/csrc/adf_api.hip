@@ -14,8 +14,9 @@ namespace adf_api {
 
 std::string g_create_error;
 
-int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out) {
+int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out, bool own_call) {
     const NetDims& c = h->net->dims;
+    if (const char* why = own_call ? nullptr : h->net->own_entry()) return fail(h, why);
     if (B < 1 || L < 1 || L % c.length_multiple) return fail(h, "length must be a positive multiple of the total down-sampling factor");
     if (adf_weights_missing(h)) return fail(h, "weights are not fully loaded");
     if (h->net->prepare(h, s) || h->net->check_image(h, L)) return 1;

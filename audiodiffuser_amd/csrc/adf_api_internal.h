@@ -6,6 +6,7 @@
 //   adf_net_adm.hip        AdmNet: ADM UNetModel (unet2d_oai.py:382-635): adf_adm_create, registry, walk
 //   adf_net_unet2d.hip     Unet2dNet: Imagen-style UNet2dBase (unet2d.py:622-972), exact fp32: adf_unet2d_create, registry, walk
 //   adf_net_dit.hip        DitNet: the adaLN-Zero transformer DiT (dit.py:278-429), exact fp32: adf_dit_create, registry, walk (kernels: adf_dit.h)
+//   adf_net_dac.hip        DacNet: dac.py::Decoder and FineTuneAutoencoder.decode, exact fp32: adf_dac_create, adf_dac_forward, the weight-norm fold (kernels: adf_dac.h)
 //   adf_walk2d.h           what the two 2-D walks share: fine GroupNorm statistics, the conv launch, the conditioning prologue
 //   adf_sampler.hip        denoise wrappers; the eleven sampler drivers (sampler_edm.py, stochastic_sampler_edm.py, sampler_rf.py), written on SamplerCtx's
 //                          members (below), which own the split between the counting pass and the real pass; count_sampler, sampler_draws; the op
@@ -134,6 +135,8 @@ struct Net {
     virtual void weight_loaded() {}                                      // a tensor was (re)loaded ...
     virtual int prepare(adf_handle* h, hipStream_t s) { (void)h; (void)s; return 0; }   // ... and what that needs before the next pass
     virtual int forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s) = 0;
+    // non-null: the net is no denoiser (the DAC decoder stack) -- why adf_net_forward, adf_denoise, the loss and the samplers refuse the handle
+    virtual const char* own_entry() const { return nullptr; }
     // n rows of the time / sigma embedding ([n][dims.temb]) from t[i * t_stride]
     virtual const char* time_embed(const float* t, int t_stride, int n, float* temb, hipStream_t s) = 0;
 };
@@ -333,7 +336,8 @@ struct Walker {
 int create_begin(const char* fn, const void* cfg, adf_handle** out);
 int create_finish(const char* fn, int dtype, std::unique_ptr<Net> net, adf_handle** out);
 int forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s);
-int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out);
+// own_call: from the entry point of a net that is no denoiser (Net::own_entry); every other caller is refused on such a handle
+int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out, bool own_call = false);
 int cond_rows(adf_handle* h, int B, bool null_branch, FwdIO& io);
 int ensure_cfg_buffers(adf_handle* h, Plan* p);
 // How one evaluation ends.  noclip: the estimate is returned as it is -- VDiffusion(for_edm=True), ReFlow: no clamp, and dynamic_threshold is never read

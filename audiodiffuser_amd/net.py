@@ -54,6 +54,10 @@ class NativeHandle:
         elif getattr(cfg, "is_dit", False):         # audiodiffuser_amd.dit.DiTConfig (dit.py imports this module)
             c = _lib.make_dit_config(cfg, _DTYPES[dtype])
             rc, what = self.lib.adf_dit_create(C.byref(c), C.byref(h)), "adf_dit_create"
+        elif getattr(cfg, "is_dac", False):         # audiodiffuser_amd.dac.DACConfig (dac.py imports this module)
+            from .dac import make_dac_config
+            c = make_dac_config(cfg, _DTYPES[dtype])
+            rc, what = self.lib.adf_dac_create(C.byref(c), C.byref(h)), "adf_dac_create"
         else:
             c = _lib.make_config(cfg, _DTYPES[dtype], flags)
             rc, what = self.lib.adf_create(C.byref(c), C.byref(h)), "adf_create"

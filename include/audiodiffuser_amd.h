@@ -23,6 +23,7 @@
  *                                     <- WaveNetNoise.forward (wavenet.py:169-180), adf_denoise / adf_sampler_run as above
  *   adf_unet2d_create              <- UNet2dBase.__init__ (src/models/backbones/unet2d.py:622-876); adf_net_forward on that handle
  *                                     <- UNet2dBase.forward (:879-972)
+ *   adf_dac_create / adf_dac_forward <- dac.py::Decoder (src/models/backbones/dac/dac.py:108-137), FineTuneAutoencoder.decode (dac_vae.py:69-71)
  *   adf_dit_create                 <- DiT.__init__ (src/models/backbones/dit.py:282-326); adf_net_forward on that handle <- DiT.forward (:382-429)
  *
  * Conventions
@@ -70,7 +71,9 @@ extern "C" {
  *    Added without a bump (new symbols only): adf_sampler_run_program and adf_sampler_program_nfe with adf_prog_desc / adf_prog_op and the ADF_PROG_*
  *    constants (VDPMSampler, VUniPCSampler).  adf_table_eval is reused as it is.  The table and the program are two public forms of one
  *    loop: the library lowers both to one internal op list and one driver runs it; neither form's structs, messages or cache keys depend on that.
- *    Added without a bump (new symbols only): adf_dit_config and adf_dit_create (DiT); everything after create is the existing surface. */
+ *    Added without a bump (new symbols only): adf_dit_config and adf_dit_create (DiT); everything after create is the existing surface.
+ *    Added without a bump (new symbols only): adf_dac_config, adf_dac_create, adf_dac_forward and adf_dac_output_length (the DAC decoder and the
+ *    decode half of FineTuneAutoencoder).  Such a handle has its own forward entry; the denoiser and sampler calls refuse it. */
 #define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
@@ -212,6 +215,44 @@ int adf_unet2d_create(const adf_unet2d_config* cfg, adf_handle** out);
  * (before unpatchify); the per-block taps exist while 3 * depth * B * T * D floats fit 512 MiB (beyond that, or with the route switch ADF_DIT_TAPS=0 in the
  * environment at create, the residual stream is updated in place and they are not kept). */
 int adf_dit_create(const adf_dit_config* cfg, adf_handle** out);
+
+/* The DAC decoder stack (added without a version bump: new symbols only), exact fp32: what turns a sampled latent into a waveform.
+ *   ADF_DAC_KIND_DECODER      dac.py::Decoder(input_channel, channels, rates, d_out = 1) (src/models/backbones/dac/dac.py:108-137): a k = 7 conv, one
+ *                             DecoderBlock per rate s (Snake, ConvTranspose1d of kernel 2 s, stride s, padding ceil(s / 2), three ResidualUnits with
+ *                             dilations 1 / 3 / 9), Snake, a k = 7 conv to one channel, tanh.  Every stage width channels / 2**i must be a multiple of 32,
+ *                             1 to 6 rates in [2, 16] (odd ones included).  A rate s maps a length L to (L - 1) s - 2 ceil(s / 2) + 2 s.
+ *   ADF_DAC_KIND_AUTOENCODER  FineTuneAutoencoder.decode (src/models/backbones/dac_vae.py:37-71) with conv_kernel = 3: input_channel is latent_dim,
+ *                             widths is intermediate_embedding_size (widths[0] = 1024, every entry a multiple of 32); channels, rates and d_out are
+ *                             not read.  btnk_layer.* and encoder_layers.* are in the registry and never read.
+ * input_channel: a multiple of 4 in [4, 2048].  State-dict keys are the reference's, with the weight-norm pair of every conv (<conv>.bias,
+ * <conv>.weight_g, <conv>.weight_v; weight_g of a ConvTranspose1d is [C_in][1][1]) and <snake>.alpha [1][C][1]; the folded weight
+ * g v / ||v|| is rebuilt before the first pass after any (re)load.  Snake is x + sin^2(alpha x) / (alpha + 1e-9), fused into the staging of the conv
+ * behind it.  Such a handle is no denoiser: adf_net_forward, adf_denoise, adf_diffusion_loss and the sampler calls refuse it with a message;
+ * adf_dac_forward is its compute call, and the weight, tap and adf_device_bytes calls serve it as they serve every handle.
+ * Debug taps (decoder): "model.0", "model.<i>" (every DecoderBlock), "model.<i>.block.1" (the transposed conv), "model.<i>.block.{2,3,4}" (the
+ * ResidualUnits), "model.<n_rates + 2>" (the value before tanh, [B][1][L_out]); the per-unit taps exist while they fit 512 MiB (beyond that, or with the
+ * route switch ADF_DAC_TAPS=0 in the environment at create, a unit adds into its input in place and only "model.0" and "model.<i>" are kept).
+ * Autoencoder: "decoder_layers.<2 i>" (every conv). */
+#define ADF_DAC_KIND_DECODER 0
+#define ADF_DAC_KIND_AUTOENCODER 1
+#define ADF_DAC_MAX_RATES 6
+#define ADF_DAC_MAX_WIDTHS 8
+typedef struct adf_dac_config {
+    int32_t kind;                           /* ADF_DAC_KIND_* */
+    int32_t input_channel;                  /* Decoder: input_channel; autoencoder: latent_dim */
+    int32_t channels;                       /* Decoder: width behind the first conv */
+    int32_t n_rates;
+    int32_t rates[ADF_DAC_MAX_RATES];
+    int32_t d_out;                          /* Decoder: 1 */
+    int32_t n_widths;
+    int32_t widths[ADF_DAC_MAX_WIDTHS];     /* autoencoder: intermediate_embedding_size */
+    int32_t dtype;                          /* ADF_DTYPE_F32 */
+} adf_dac_config;
+int adf_dac_create(const adf_dac_config* cfg, adf_handle** out);
+/* in: fp32 [B][input_channel][T] on the handle's device; out: fp32 [B][1][adf_dac_output_length(h, T)] (decoder) or [B][1024][T] (autoencoder).
+ * Enqueued on `stream`; allocates only when (B, T) is new to the handle, so a later call with the same shape can be captured in a graph. */
+int adf_dac_forward(adf_handle* h, const float* in, int B, int T, float* out, void* stream);
+int64_t adf_dac_output_length(const adf_handle* h, int T);     /* -1: not a DAC handle, or T < 1 */
 int adf_set_image_shape(adf_handle* h, int H, int W);
 
 /* Clipping of every denoiser evaluation from here on (adf_denoise, adf_sampler_run): 0 = clamp to [-1, 1] (the default), q in (0, 1] = the dynamic
