@@ -136,7 +136,8 @@ class AdfDitConfig(C.Structure):
 
 
 ADF_DAC_MAX_RATES, ADF_DAC_MAX_WIDTHS = 6, 8
-DAC_KIND_DECODER, DAC_KIND_AUTOENCODER = 0, 1
+DAC_KIND_DECODER, DAC_KIND_AUTOENCODER, DAC_KIND_ENCODER = 0, 1, 2
+DAC_BTNK_TANH = 2          # AdfDacConfig.d_out of an autoencoder with tanh_btnk=True
 
 
 class AdfDacConfig(C.Structure):
@@ -177,6 +178,7 @@ EXPORTS = {
     "adf_dac_create": (C.c_int, [C.POINTER(AdfDacConfig), C.POINTER(C.c_void_p)]),
     "adf_dac_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "adf_dac_output_length": (C.c_int64, [C.c_void_p, C.c_int]),
+    "adf_dac_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "adf_set_image_shape": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "adf_set_dynamic_threshold": (C.c_int, [C.c_void_p, C.c_float]),
     "adf_set_preconditioning": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]),

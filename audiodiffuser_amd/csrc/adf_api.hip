@@ -14,20 +14,20 @@ namespace adf_api {
 
 std::string g_create_error;
 
-int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out, bool own_call) {
+int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out, bool own_call, int variant) {
     const NetDims& c = h->net->dims;
     if (const char* why = own_call ? nullptr : h->net->own_entry()) return fail(h, why);
     if (B < 1 || L < 1 || L % c.length_multiple) return fail(h, "length must be a positive multiple of the total down-sampling factor");
     if (adf_weights_missing(h)) return fail(h, "weights are not fully loaded");
     if (h->net->prepare(h, s) || h->net->check_image(h, L)) return 1;
-    const std::tuple<int, int, int> pkey{B, L, h->net->image ? h->net->H : 0};
+    const std::tuple<int, int, int> pkey{B, L, h->net->image ? h->net->H : variant};
     auto it = h->plans.find(pkey);
     if (it != h->plans.end()) { *out = it->second; h->last_plan = it->second; it->second->last_use = ++h->use_clock; return 0; }
     Plan* p = new Plan();
     p->B = B; p->L = L;
     p->dry = true;
     FwdIO io;
-    io.nb = B;
+    io.nb = B; io.variant = variant;
     if (forward(h, p, io, s)) { delete p; return 1; }
     // a long-running caller with varying batch sizes / lengths must not accumulate workspaces: release the least recently
     // used plan first (its graphs and buffers may still be referenced by queued work: drain the device before freeing)

@@ -6,7 +6,7 @@
 //   adf_net_adm.hip        AdmNet: ADM UNetModel (unet2d_oai.py:382-635): adf_adm_create, registry, walk
 //   adf_net_unet2d.hip     Unet2dNet: Imagen-style UNet2dBase (unet2d.py:622-972), exact fp32: adf_unet2d_create, registry, walk
 //   adf_net_dit.hip        DitNet: the adaLN-Zero transformer DiT (dit.py:278-429), exact fp32: adf_dit_create, registry, walk (kernels: adf_dit.h)
-//   adf_net_dac.hip        DacNet: dac.py::Decoder and FineTuneAutoencoder.decode, exact fp32: adf_dac_create, adf_dac_forward, the weight-norm fold (kernels: adf_dac.h)
+//   adf_net_dac.hip        DacNet: dac.py::Decoder, dac.py::Encoder and FineTuneAutoencoder.decode / .encode, exact fp32: adf_dac_create, adf_dac_forward, adf_dac_encode, the weight-norm fold (kernels: adf_dac.h)
 //   adf_walk2d.h           what the two 2-D walks share: fine GroupNorm statistics, the conv launch, the conditioning prologue
 //   adf_sampler.hip        denoise wrappers; the eleven sampler drivers (sampler_edm.py, stochastic_sampler_edm.py, sampler_rf.py), written on SamplerCtx's
 //                          members (below), which own the split between the counting pass and the real pass; count_sampler, sampler_draws; the op
@@ -108,6 +108,8 @@ struct FwdIO {
     const float* film_pre = nullptr;                       // this evaluation's row of Plan::film_all: sigma embedding + FiLM already computed
     const float* temb_pre = nullptr;                       // this evaluation's row of Plan::temb_all (class-conditional ADM net: the FiLM rows are per sample)
     bool null_cond = false;                                // class-conditional ADM net: every sample takes the null class embedding (guidance branch)
+    float* aux = nullptr;                                  // a second result of a net with its own entry point (adf_dac_encode: the KL term, one float)
+    int variant = 0;                                       // which walk of a net that walks one (B, L) in more than one way (DAC autoencoder: 0 decode, 1 encode)
 };
 
 // What the shared plan, condition and sampler code reads of a network.  The create call fills it once; nothing else writes it.
@@ -178,7 +180,7 @@ struct adf_handle {
     float* cond_emb = nullptr;          // [cond_B + 1][cdim], last row = null embedding
     float* cond_film = nullptr;         // [cond_B + 1][film_total]: class part of every FiLM projection
     int cond_cap = 0;
-    // (B, L, H): H = image height of an image net (W = L / H), 0 otherwise -- two image shapes with equal H * W must not share
+    // (B, L, H): H = image height of an image net (W = L / H), the FwdIO::variant the plan was built for otherwise (0 but for a DAC autoencoder's encode) -- two image shapes with equal H * W must not share
     // a workspace: captured graphs and tap shapes carry the conv2d geometry
     std::map<std::tuple<int, int, int>, Plan*> plans;
     Plan* last_plan = nullptr;
@@ -337,7 +339,8 @@ int create_begin(const char* fn, const void* cfg, adf_handle** out);
 int create_finish(const char* fn, int dtype, std::unique_ptr<Net> net, adf_handle** out);
 int forward(adf_handle* h, Plan* p, const FwdIO& io, hipStream_t s);
 // own_call: from the entry point of a net that is no denoiser (Net::own_entry); every other caller is refused on such a handle
-int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out, bool own_call = false);
+// variant: FwdIO::variant of the walk the workspace is for (its dry pass and warm-up run with it); part of the plan's key
+int get_plan(adf_handle* h, int B, int L, hipStream_t s, Plan** out, bool own_call = false, int variant = 0);
 int cond_rows(adf_handle* h, int B, bool null_branch, FwdIO& io);
 int ensure_cfg_buffers(adf_handle* h, Plan* p);
 // How one evaluation ends.  noclip: the estimate is returned as it is -- VDiffusion(for_edm=True), ReFlow: no clamp, and dynamic_threshold is never read

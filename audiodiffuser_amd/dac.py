@@ -1,5 +1,6 @@
-"""HIP-backed drop-ins for the reference's DAC decoder stack: ``dac.py::Decoder`` (src/models/backbones/dac/dac.py:108-137) as ``DACDecoder`` and the
-decode half of ``FineTuneAutoencoder`` (src/models/backbones/dac_vae.py:11-77).  ``dec(ae.decode(latents))`` is the path from a sampled latent to audio.
+"""HIP-backed drop-ins for the reference's DAC stacks: ``dac.py::Decoder`` (src/models/backbones/dac/dac.py:108-137) as ``DACDecoder``,
+``dac.py::Encoder`` (:57-84) as ``DACEncoder`` and ``FineTuneAutoencoder`` (src/models/backbones/dac_vae.py:11-77).  ``dec(ae.decode(latents))`` is the
+path from a sampled latent to audio; ``ae.encode(enc(audio), is_train=False)`` is the path from audio to the latent a latent net is trained and validated on.
 
 Contract kept: the positional constructor arguments and defaults, ``state_dict()`` keys / order / shapes (the old-style weight-norm pair ``weight_g`` /
 ``weight_v`` of every conv behind its ``bias``; ``alpha`` of every Snake as ``[1, C, 1]``), so a slice of a reference checkpoint strict-loads.  Exact fp32
@@ -29,22 +30,37 @@ def up_length(L: int, s: int) -> int:
     return (L - 1) * s - 2 * math.ceil(s / 2) + 2 * s
 
 
+def down_min_length(s: int) -> int:
+    """Shortest input ``Conv1d(kernel 2 s, stride s, padding ceil(s / 2))`` serves: ``s`` for even ``s``, ``s - 1`` for odd ``s``."""
+    return 2 * s - 2 * math.ceil(s / 2)
+
+
+def down_length(L: int, s: int) -> int:
+    """Length behind ``Conv1d(kernel 2 s, stride s, padding ceil(s / 2))``: ``L // s`` for even ``s``, ``(L + 1) // s`` for odd ``s``."""
+    return (L + 2 * math.ceil(s / 2) - 2 * s) // s + 1
+
+
 @dataclass
 class DACConfig:
-    """What the library is told about one DAC handle (``adf_dac_config``): ``kind`` 0 the decoder, 1 the autoencoder's decode stack."""
+    """What the library is told about one DAC handle (``adf_dac_config``): ``kind`` 0 the decoder, 1 the autoencoder, 2 the encoder."""
     kind: int = 0
-    input_channel: int = 1024           # decoder: input_channel; autoencoder: latent_dim
-    channels: int = 1536
-    rates: List[int] = field(default_factory=list)
-    d_out: int = 1
+    input_channel: int = 1024           # decoder: input_channel; autoencoder: latent_dim; encoder: 1
+    channels: int = 1536                # encoder: d_model
+    rates: List[int] = field(default_factory=list)       # encoder: strides
+    d_out: int = 1                      # encoder: d_latent; autoencoder: 2 (ADF_DAC_BTNK_TANH) with tanh_btnk
     widths: List[int] = field(default_factory=list)      # autoencoder: intermediate_embedding_size
 
     is_dac = True                       # what NativeHandle keys its create call on
     class_cond = False
 
     def output_length(self, T: int) -> int:
-        for s in self.rates:
-            T = up_length(T, s)
+        for i, s in enumerate(self.rates):
+            if self.kind == 2:
+                if T < down_min_length(s):
+                    raise ValueError(f"L is too short: the strided conv of stage {i} (stride {s}) needs at least {down_min_length(s)} positions, has {T}")
+                T = down_length(T, s)
+            else:
+                T = up_length(T, s)
         return T
 
     @property
@@ -53,6 +69,14 @@ class DACConfig:
 
     def validate_device(self) -> None:
         """What the kernels serve (csrc/adf_dac.h), reported against the constructor argument that sets it."""
+        if self.kind == 2:
+            if not 1 <= len(self.rates) <= MAX_RATES or any(int(s) != s or not 2 <= s <= 16 for s in self.rates):
+                raise ValueError(f"strides={list(self.rates)} must be 1 to {MAX_RATES} integers in [2, 16]")
+            if self.channels < 32 or self.channels % 32 or self.channels << len(self.rates) > 8192:
+                raise ValueError(f"d_model={self.channels} must be a multiple of 32 with d_model * 2**len(strides) <= 8192")
+            if self.d_out < 32 or self.d_out % 32 or self.d_out > 8192:
+                raise ValueError(f"d_latent={self.d_out} must be a multiple of 32 in [32, 8192]")
+            return
         ic = "latent_dim" if self.kind == 1 else "input_channel"
         if self.input_channel < 4 or self.input_channel % 4 or self.input_channel > 2048:
             raise ValueError(f"{ic}={self.input_channel} must be a multiple of 4 in [4, 2048]")
@@ -93,6 +117,25 @@ def decoder_specs(cfg: DACConfig) -> "OrderedDict[str, Spec]":
     n, cl = len(cfg.rates), cfg.channels // 2 ** len(cfg.rates)
     out[f"model.{n + 1}.alpha"] = ((1, cl, 1), "alpha")
     _wn_conv(out, f"model.{n + 2}", cl, cfg.d_out, 7)
+    return out
+
+
+def encoder_specs(cfg: DACConfig) -> "OrderedDict[str, Spec]":
+    """Every ``Encoder.state_dict()`` key with its shape, in the module's order (dac.py:66-80)."""
+    out: "OrderedDict[str, Spec]" = OrderedDict()
+    _wn_conv(out, "block.0", 1, cfg.channels, 7)
+    for i, s in enumerate(cfg.rates):
+        c, p = cfg.channels * 2 ** i, f"block.{i + 1}.block"
+        for u in range(3):
+            out[f"{p}.{u}.block.0.alpha"] = ((1, c, 1), "alpha")
+            _wn_conv(out, f"{p}.{u}.block.1", c, c, 7)
+            out[f"{p}.{u}.block.2.alpha"] = ((1, c, 1), "alpha")
+            _wn_conv(out, f"{p}.{u}.block.3", c, c, 1, kind="pw")
+        out[f"{p}.3.alpha"] = ((1, c, 1), "alpha")
+        _wn_conv(out, f"{p}.4", c, 2 * c, 2 * s, kind="down")
+    n, cl = len(cfg.rates), cfg.channels * 2 ** len(cfg.rates)
+    out[f"block.{n + 1}.alpha"] = ((1, cl, 1), "alpha")
+    _wn_conv(out, f"block.{n + 2}", cl, cfg.d_out, 3)
     return out
 
 
@@ -145,11 +188,11 @@ class _DacNet(HipNet):
         if torch.is_grad_enabled() and x.requires_grad:
             raise NotImplementedError(f"the HIP {type(self).__name__} is an inference path (no backward); call it under torch.no_grad()")
         if x.ndim != 3 or x.shape[1] != self.cfg.input_channel or x.shape[0] < 1 or x.shape[2] < 1:
-            raise ValueError(f"{what} must be shaped [B, {self.cfg.input_channel}, T]")
+            raise ValueError(f"{what} must be shaped [B, {self.cfg.input_channel}, {'L' if self.cfg.kind == 2 else 'T'}]")
+        B, T = int(x.shape[0]), int(x.shape[2])
+        shape = (B, self.cfg.widths[0], T) if self.cfg.kind == 1 else (B, self.cfg.d_out, self.cfg.output_length(T))      # (encoder: refuses a short L)
         hd = self.native(x.device)
         xin = x.detach().to(torch.float32).contiguous()
-        B, T = int(xin.shape[0]), int(xin.shape[2])
-        shape = (B, self.cfg.widths[0], T) if self.cfg.kind == 1 else (B, self.cfg.d_out, self.cfg.output_length(T))
         out = torch.empty(shape, device=x.device, dtype=torch.float32)
         with torch.cuda.device(x.device):
             hd.check(hd.lib.adf_dac_forward(hd.h, C.c_void_p(xin.data_ptr()), B, T, C.c_void_p(out.data_ptr()), C.c_void_p(_stream_ptr(x.device))),
@@ -177,25 +220,69 @@ class DACDecoder(_DacNet):
         return self._run(z, "z")
 
 
+class DACEncoder(_DacNet):
+    """HIP-backed ``dac.py::Encoder``: ``forward(audio)`` takes ``[B, 1, L]`` on a ROCm device and returns ``[B, d_latent, output_length(L)]``.
+    On the device: ``d_model`` a multiple of 32 with ``d_model * 2**len(strides) <= 8192``, ``d_latent`` a multiple of 32 in [32, 8192], 1 to 6
+    strides in [2, 16] (odd ones included).  With a DAC checkpoint: ``load_state_dict({k[len("encoder."):]: v for k, v in sd.items() if
+    k.startswith("encoder.")})``."""
+
+    def __init__(self, d_model: int = 64, strides: list = [2, 4, 8, 8], d_latent: int = 64):
+        super().__init__()
+        self._build(DACConfig(kind=2, input_channel=1, channels=int(d_model), rates=list(strides), d_out=int(d_latent)), encoder_specs)
+        self.enc_dim = self.cfg.channels * 2 ** len(self.cfg.rates)
+
+    def output_length(self, L: int) -> int:
+        """Frames per item that ``forward`` returns for ``L`` samples: each stride ``s`` maps ``L`` to ``floor((L + 2 ceil(s / 2) - 2 s) / s) + 1``
+        and needs ``L >= 2 s - 2 ceil(s / 2)`` (``ValueError`` naming ``L`` otherwise)."""
+        return self.cfg.output_length(int(L))
+
+    def forward(self, audio: torch.Tensor) -> torch.Tensor:
+        return self._run(audio, "audio")
+
+
 class FineTuneAutoencoder(_DacNet):
-    """HIP-backed ``FineTuneAutoencoder``: the full state dict loads (``btnk_layer.*`` and ``encoder_layers.*`` are never read); ``decode(x)`` takes
-    ``[B, latent_dim, T]`` on a ROCm device and returns the DAC embedding ``[B, 1024, T]``.  ``encode`` / ``forward`` are training-side."""
+    """HIP-backed ``FineTuneAutoencoder``.  ``decode(x)`` takes ``[B, latent_dim, T]`` on a ROCm device and returns the DAC embedding ``[B, 1024, T]``.
+    ``encode(x, is_train=False)`` takes that embedding and returns ``(mean [B, latent_dim, T], kl)``; ``forward(x, is_train=False)`` returns
+    ``(decode(mean), kl)``.  Pass ``is_train=False``: the default ``is_train=True`` draws ``randn_like`` (training-side) and is refused."""
 
     def __init__(self, intermediate_embedding_size=[1024, 512, 256, 128], conv_kernel=3, tanh_btnk=False, latent_dim=32):
         super().__init__()
         if conv_kernel != 3:
             raise ValueError(f"conv_kernel={conv_kernel}: with the reference's fixed padding=1 only 3 keeps the length")
         self.tanh_btnk = tanh_btnk
-        self._build(DACConfig(kind=1, input_channel=int(latent_dim), widths=[int(c) for c in intermediate_embedding_size]), autoencoder_specs)
+        self._build(DACConfig(kind=1, input_channel=int(latent_dim), widths=[int(c) for c in intermediate_embedding_size],
+                              d_out=_lib.DAC_BTNK_TANH if tanh_btnk else 1), autoencoder_specs)
 
     def decode(self, x: torch.Tensor) -> torch.Tensor:
         return self._run(x, "x")
 
     def encode(self, x, is_train=True):
-        raise NotImplementedError("FineTuneAutoencoder.encode (VAE sampling and the KL term) is training-side and not on the device path")
+        """``(mean, kl_loss_value)`` of the reference's ``encode(x, is_train=False)``: ``x`` is ``[B, 1024, T]``, mean ``[B, latent_dim, T]`` (tanh of it
+        with ``tanh_btnk``), kl a 0-dim tensor.  Pass ``is_train=False``: sampling from (mean, logvar) is training-side."""
+        if is_train:
+            raise NotImplementedError("FineTuneAutoencoder.encode with is_train=True (VAE sampling) is training-side and not on the device path; "
+                                      "pass is_train=False")
+        if torch.is_grad_enabled() and x.requires_grad:
+            raise NotImplementedError(f"the HIP {type(self).__name__} is an inference path (no backward); call it under torch.no_grad()")
+        if x.ndim != 3 or x.shape[1] != self.cfg.widths[0] or x.shape[0] < 1 or x.shape[2] < 1:
+            raise ValueError(f"x must be shaped [B, {self.cfg.widths[0]}, T]")
+        hd = self.native(x.device)
+        xin = x.detach().to(torch.float32).contiguous()
+        B, T = int(xin.shape[0]), int(xin.shape[2])
+        mean = torch.empty((B, self.cfg.input_channel, T), device=x.device, dtype=torch.float32)
+        kl = torch.empty((), device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            hd.check(hd.lib.adf_dac_encode(hd.h, C.c_void_p(xin.data_ptr()), B, T, C.c_void_p(mean.data_ptr()), C.c_void_p(kl.data_ptr()),
+                                           C.c_void_p(_stream_ptr(x.device))), "adf_dac_encode")
+        return mean.to(x.dtype), kl.to(x.dtype)
 
     def forward(self, x, is_train=True):
-        raise NotImplementedError("FineTuneAutoencoder.forward encodes first (training-side); call decode(latents)")
+        """``(decode(mean), kl_loss_value)`` of the reference's ``forward(x, is_train=False)``.  Pass ``is_train=False``."""
+        if is_train:
+            raise NotImplementedError("FineTuneAutoencoder.forward with is_train=True samples the latent (training-side); pass is_train=False, "
+                                      "or call decode(latents)")
+        mean, kl = self.encode(x, is_train=False)
+        return self.decode(mean), kl
 
 
 def make_dac_config(cfg: DACConfig, dtype: int) -> "_lib.AdfDacConfig":

@@ -23,7 +23,8 @@
  *                                     <- WaveNetNoise.forward (wavenet.py:169-180), adf_denoise / adf_sampler_run as above
  *   adf_unet2d_create              <- UNet2dBase.__init__ (src/models/backbones/unet2d.py:622-876); adf_net_forward on that handle
  *                                     <- UNet2dBase.forward (:879-972)
- *   adf_dac_create / adf_dac_forward <- dac.py::Decoder (src/models/backbones/dac/dac.py:108-137), FineTuneAutoencoder.decode (dac_vae.py:69-71)
+ *   adf_dac_create / adf_dac_forward <- dac.py::Decoder (src/models/backbones/dac/dac.py:108-137), dac.py::Encoder (:57-84), FineTuneAutoencoder.decode (dac_vae.py:69-71)
+ *   adf_dac_encode                 <- FineTuneAutoencoder.encode(x, is_train=False) (dac_vae.py:50-67)
  *   adf_dit_create                 <- DiT.__init__ (src/models/backbones/dit.py:282-326); adf_net_forward on that handle <- DiT.forward (:382-429)
  *
  * Conventions
@@ -73,7 +74,9 @@ extern "C" {
  *    loop: the library lowers both to one internal op list and one driver runs it; neither form's structs, messages or cache keys depend on that.
  *    Added without a bump (new symbols only): adf_dit_config and adf_dit_create (DiT); everything after create is the existing surface.
  *    Added without a bump (new symbols only): adf_dac_config, adf_dac_create, adf_dac_forward and adf_dac_output_length (the DAC decoder and the
- *    decode half of FineTuneAutoencoder).  Such a handle has its own forward entry; the denoiser and sampler calls refuse it. */
+ *    decode half of FineTuneAutoencoder).  Such a handle has its own forward entry; the denoiser and sampler calls refuse it.
+ *    Added without a bump (a new symbol and a new value of an existing field): adf_dac_encode and ADF_DAC_KIND_ENCODER (the DAC encoder and the
+ *    encode half of FineTuneAutoencoder), on the unchanged adf_dac_config layout. */
 #define ADF_ABI_VERSION 7
 int adf_abi_version(void);
 
@@ -222,9 +225,18 @@ int adf_dit_create(const adf_dit_config* cfg, adf_handle** out);
  *                             dilations 1 / 3 / 9), Snake, a k = 7 conv to one channel, tanh.  Every stage width channels / 2**i must be a multiple of 32,
  *                             1 to 6 rates in [2, 16] (odd ones included).  A rate s maps a length L to (L - 1) s - 2 ceil(s / 2) + 2 s.
  *   ADF_DAC_KIND_AUTOENCODER  FineTuneAutoencoder.decode (src/models/backbones/dac_vae.py:37-71) with conv_kernel = 3: input_channel is latent_dim,
- *                             widths is intermediate_embedding_size (widths[0] = 1024, every entry a multiple of 32); channels, rates and d_out are
- *                             not read.  btnk_layer.* and encoder_layers.* are in the registry and never read.
- * input_channel: a multiple of 4 in [4, 2048].  State-dict keys are the reference's, with the weight-norm pair of every conv (<conv>.bias,
+ *                             widths is intermediate_embedding_size (widths[0] = 1024, every entry a multiple of 32); channels and rates are
+ *                             not read.  adf_dac_forward (decode) reads neither btnk_layer.* nor encoder_layers.*.
+ *                             With adf_dac_encode the handle also serves FineTuneAutoencoder.encode(x, is_train=False): encoder_layers.* (Snake, k = 3
+ *                             conv per width) and btnk_layer (a plain 1x1 conv to 2 latent_dim channels) are folded like the rest; d_out =
+ *                             ADF_DAC_BTNK_TANH is tanh_btnk=True (any other value: False).
+ *   ADF_DAC_KIND_ENCODER      dac.py::Encoder(d_model, strides, d_latent) (dac.py:57-84): input_channel = 1, channels = d_model, rates = strides,
+ *                             d_out = d_latent.  A k = 7 conv from the waveform, one EncoderBlock per stride s (three ResidualUnits with dilations
+ *                             1 / 3 / 9, Snake, Conv1d of kernel 2 s, stride s, padding ceil(s / 2) that doubles the width), Snake, a k = 3 conv to
+ *                             d_latent.  d_model a multiple of 32 with d_model * 2**n_rates <= 8192, d_latent a multiple of 32 in [32, 8192], 1 to 6
+ *                             strides in [2, 16].  A stride s maps a length L to floor((L + 2 ceil(s / 2) - 2 s) / s) + 1 (L / s for even s,
+ *                             (L + 1) / s for odd s) and needs L >= 2 s - 2 ceil(s / 2); adf_dac_forward refuses a shorter L by name.
+ * input_channel (decoder, autoencoder): a multiple of 4 in [4, 2048].  State-dict keys are the reference's, with the weight-norm pair of every conv (<conv>.bias,
  * <conv>.weight_g, <conv>.weight_v; weight_g of a ConvTranspose1d is [C_in][1][1]) and <snake>.alpha [1][C][1]; the folded weight
  * g v / ||v|| is rebuilt before the first pass after any (re)load.  Snake is x + sin^2(alpha x) / (alpha + 1e-9), fused into the staging of the conv
  * behind it.  Such a handle is no denoiser: adf_net_forward, adf_denoise, adf_diffusion_loss and the sampler calls refuse it with a message;
@@ -232,27 +244,37 @@ int adf_dit_create(const adf_dit_config* cfg, adf_handle** out);
  * Debug taps (decoder): "model.0", "model.<i>" (every DecoderBlock), "model.<i>.block.1" (the transposed conv), "model.<i>.block.{2,3,4}" (the
  * ResidualUnits), "model.<n_rates + 2>" (the value before tanh, [B][1][L_out]); the per-unit taps exist while they fit 512 MiB (beyond that, or with the
  * route switch ADF_DAC_TAPS=0 in the environment at create, a unit adds into its input in place and only "model.0" and "model.<i>" are kept).
- * Autoencoder: "decoder_layers.<2 i>" (every conv). */
+ * Autoencoder: "decoder_layers.<2 i>" (every conv); after adf_dac_encode "encoder_layers.<2 i + 1>" (every conv) and "btnk_layer" (the raw
+ * [B][2 latent_dim][T] before chunk, clamp and tanh).  Encoder: "block.0", "block.<i>" (every EncoderBlock), "block.<i>.block.{0,1,2}" (the
+ * ResidualUnits, under the same 512 MiB / ADF_DAC_TAPS rule), "block.<n_rates + 2>" (the result). */
 #define ADF_DAC_KIND_DECODER 0
 #define ADF_DAC_KIND_AUTOENCODER 1
+#define ADF_DAC_KIND_ENCODER 2
+#define ADF_DAC_BTNK_TANH 2                 /* adf_dac_config::d_out of an autoencoder built with tanh_btnk=True */
 #define ADF_DAC_MAX_RATES 6
 #define ADF_DAC_MAX_WIDTHS 8
 typedef struct adf_dac_config {
     int32_t kind;                           /* ADF_DAC_KIND_* */
-    int32_t input_channel;                  /* Decoder: input_channel; autoencoder: latent_dim */
-    int32_t channels;                       /* Decoder: width behind the first conv */
+    int32_t input_channel;                  /* Decoder: input_channel; autoencoder: latent_dim; encoder: 1 */
+    int32_t channels;                       /* Decoder: width behind the first conv; encoder: d_model */
     int32_t n_rates;
     int32_t rates[ADF_DAC_MAX_RATES];
-    int32_t d_out;                          /* Decoder: 1 */
+    int32_t d_out;                          /* Decoder: 1; encoder: d_latent; autoencoder: ADF_DAC_BTNK_TANH or anything else */
     int32_t n_widths;
     int32_t widths[ADF_DAC_MAX_WIDTHS];     /* autoencoder: intermediate_embedding_size */
     int32_t dtype;                          /* ADF_DTYPE_F32 */
 } adf_dac_config;
 int adf_dac_create(const adf_dac_config* cfg, adf_handle** out);
-/* in: fp32 [B][input_channel][T] on the handle's device; out: fp32 [B][1][adf_dac_output_length(h, T)] (decoder) or [B][1024][T] (autoencoder).
+/* in: fp32 [B][input_channel][T] on the handle's device; out: fp32 [B][1][adf_dac_output_length(h, T)] (decoder), [B][1024][T] (autoencoder) or
+ * [B][d_latent][adf_dac_output_length(h, T)] (encoder: in is the waveform [B][1][T]).
  * Enqueued on `stream`; allocates only when (B, T) is new to the handle, so a later call with the same shape can be captured in a graph. */
 int adf_dac_forward(adf_handle* h, const float* in, int B, int T, float* out, void* stream);
-int64_t adf_dac_output_length(const adf_handle* h, int T);     /* -1: not a DAC handle, or T < 1 */
+int64_t adf_dac_output_length(const adf_handle* h, int T);     /* -1: not a DAC handle, T < 1, or (encoder) T too short for a stage */
+/* FineTuneAutoencoder.encode(x, is_train=False) on an ADF_DAC_KIND_AUTOENCODER handle (any other handle is refused with a message): in fp32
+ * [B][1024][T]; mean_out fp32 [B][latent_dim][T] (tanh of it under ADF_DAC_BTNK_TANH); kl_out one fp32 on the device:
+ * 0.5 mean_b sum_{c, t} (mean^2 + exp(logvar) - logvar - 1) with logvar clamped to [-30, 20], summed in a fixed order (bit-reproducible, no atomics).
+ * Enqueued on `stream`; allocates only when (B, T) is new to encode on this handle.  adf_dac_forward (decode) on the same handle is unaffected. */
+int adf_dac_encode(adf_handle* h, const float* in, int B, int T, float* mean_out, float* kl_out, void* stream);
 int adf_set_image_shape(adf_handle* h, int H, int W);
 
 /* Clipping of every denoiser evaluation from here on (adf_denoise, adf_sampler_run): 0 = clamp to [-1, 1] (the default), q in (0, 1] = the dynamic
